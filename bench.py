@@ -12,9 +12,15 @@ default-initialised weights.  One "step" = the reference's training iteration (l
 forward, masked de-normalised L1, backward, Adam step, gradients cleared -- with the scalar loss kept on the
 device and read back after the timed region (the reference's per-step loss.item() would only add a host sync).
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel class, timed with HIP events on the
-launch stream over the timed region (rd_prof_*, include/resdepth_hip.h); `cpu_baseline` is the oracle
-(torch-CPU restatement of the reference step) on a bounded sample on this box's host cores.
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, warm-up, the K timed steps and
+the line (`value`, `ms_per_step`, per-step HIP-event times, losses).  `--full` adds everything else after the timed
+region: the diagnostics pass (host enqueue time; under data parallelism the exposed exchanges and the tuning pass), the
+serialized per-kernel pass behind `roofline` / `kernels` (HIP events on the launch stream, rd_prof_*,
+include/resdepth_hip.h), the `secondary` workloads and arithmetics, and `cpu_baseline` (the oracle, a torch-CPU
+restatement of the reference step, on a bounded sample on this box's host cores).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_train_outputs /
+dump_infer_outputs): the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -22,6 +28,8 @@ import os
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 # RCCL on these hosts: the kernel driver supports only dmabuf IPC handles; with the legacy IPC mode RCCL's intra-node
 # peer-to-peer set-up (and any sharing of device tensors between processes) fails with `hipIpcGetMemHandle: invalid
@@ -232,6 +240,51 @@ def cpu_baseline(warm=1, timed=3, batch=32):
                       f"hardware threads (thread count: the better of the two best settings of an in-run sweep at batch 8)"}
 
 
+# --dump-outputs: at most 64 MB in all.  An array longer than its cap is written as a fixed sample (seed 0, sorted indices),
+# the same elements in every run of the same arguments
+DUMP_MAX_BYTES = 64_000_000
+DUMP_PARAMS_MAX = 13_000_000          # cfg-S has 12 625 345 parameters: written whole
+DUMP_MOMENTS_MAX = 2_000_000
+DUMP_RASTER_MAX = 4_000_000           # float64 pixels (cfg-G's 8192^2 raster is 67 M)
+
+
+def _dump_array(path, name, t, max_elems):
+    """Flatten `t` (tensor or ndarray), keep a seeded sample of `max_elems` elements if it is longer, write DIR/name.npy as
+    float32 (float32 sources) or float64 (everything else).  -> bytes written."""
+    t = torch.as_tensor(t).detach().reshape(-1)
+    if t.numel() > max_elems:
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), max_elems, replace=False))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    a = t.cpu().numpy().astype(np.float32 if t.dtype == torch.float32 else np.float64)
+    np.save(os.path.join(path, name + ".npy"), a)
+    return a.nbytes
+
+
+def dump_train_outputs(path, tb):
+    """What a caller of the timed training step holds after its last step: the loss it returned, the model's parameters after
+    the optimizer update and its BatchNorm running statistics, and Adam's first moments (what the step's gradients left in the
+    optimizer state).  Parameters and moments are flattened in model.parameters() order."""
+    os.makedirs(path, exist_ok=True)
+    params = list(tb.model.parameters())
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1) for p in params])
+        moments = torch.cat([tb.opt.state[p]["exp_avg"].detach().reshape(-1) for p in params])
+        bufs = [b.detach().reshape(-1) for n, b in tb.model.named_buffers() if b.is_floating_point()]
+        nbytes = _dump_array(path, "loss", tb.losses[-1], 1)
+        nbytes += _dump_array(path, "params", flat, DUMP_PARAMS_MAX)
+        nbytes += _dump_array(path, "adam_exp_avg", moments, DUMP_MOMENTS_MAX)
+        if bufs:
+            nbytes += _dump_array(path, "bn_running_stats", torch.cat(bufs), DUMP_PARAMS_MAX)
+    assert nbytes <= DUMP_MAX_BYTES, nbytes
+
+
+def dump_infer_outputs(path, raster):
+    """cfg-G: the blended raster of the last timed sweep (float64, what predict_linear_blend returns), row-major."""
+    os.makedirs(path, exist_ok=True)
+    nbytes = _dump_array(path, "raster", raster, DUMP_RASTER_MAX)
+    assert nbytes <= DUMP_MAX_BYTES, nbytes
+
+
 def infer_main(args, world, rank, dev):
     """cfg-G: forward-only sweep of a raster with overlapping tiles + linear blend (lib/evaluation.py:460-513).
     `steps` = number of full sweeps timed.  Tiles are sharded over the ranks by row bands (resdepth_amd.tiling.band_shards):
@@ -274,6 +327,8 @@ def infer_main(args, world, rank, dev):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     checksum = float(out.sum())
+    if args.dump_outputs and rank == 0:         # the complete raster is on rank 0
+        dump_infer_outputs(args.dump_outputs, out)
     kern = []
     if not args.no_prof:        # one more sweep, instrumented with HIP events per kernel class (never part of `value`)
         _lib.prof_reset(); _lib.prof_enable(2)
@@ -1060,9 +1115,20 @@ def main():
     ap.add_argument("--no-pin", action="store_true",
                     help="N > 1: do not bind the rank to the CPUs of its GPU's NUMA node (pin_rank_to_gpu_numa)")
     ap.add_argument("--diag-steps", type=int, default=5,
-                    help="steps of the diagnostics pass after the timed region (host enqueue time; N > 1 / --force-dist: exposed "
-                         "all-reduce wait, loss-normaliser latency, bucket issue times); 0 = skip")
+                    help="--full: steps of the diagnostics pass after the timed region (host enqueue time; N > 1 / --force-dist: "
+                         "exposed all-reduce wait, loss-normaliser latency, bucket issue times); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the diagnostics pass, the serialized per-kernel roofline pass, the "
+                         "secondary workloads / arithmetics and the CPU baseline (each still subject to its --no-* / --diag-steps "
+                         "option); default: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, at most 64 MB, "
+                         "a fixed seeded sample of larger arrays)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run is the headline alone: set up, warm up, time the steps, dump the outputs if asked, print the line
+        args.no_cpu_baseline = args.no_secondary = args.no_prof = True
+        args.diag_steps = 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1136,6 +1202,8 @@ def main():
         torch.cuda.synchronize()
     dt, step_ms = tb.timed(args.steps, args.warmup, barrier)
     timed_losses = list(tb.losses)
+    if args.dump_outputs and rank == 0:          # before anything below takes another step
+        dump_train_outputs(args.dump_outputs, tb)
     plan_info = {"enabled": bool(tb.use_plan), "replays": tb.plan.replays, "launches": tb.plan.n_launches, "segments": tb.plan.n_segments,
                  "last_eager_reason": tb.plan.why_eager, "rejected": getattr(tb.plan, "plan_rejected", None),
                  "note": "the iteration's ~110 kernel launches recorded once (under a graph capture, for its reserved memory) and "

@@ -6,7 +6,7 @@ for r in $(seq 1 "$R"); do
   for L in "$@"; do
     tag=$(basename "$L" .so)
     if [ "$L" = "-" ]; then unset RESDEPTH_HIP_LIB; tag=tree; else export RESDEPTH_HIP_LIB="$(pwd)/$L"; fi
-    python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "
+    python bench.py --steps 30 --warmup 8 --full --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 rows = {k['name']: k['ms_per_step'] for k in d['kernels'] if 'hbm_frac' in k}

@@ -5,6 +5,6 @@
 # (ablate_libs/ is git-ignored but travels with gpurun).  Prints tiles/s, the dominant kernel's TFLOP/s and launch time.
 for r in 1 2 3; do
   for T in . ablate_libs/old_tree; do
-    (cd $T && python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$T', d['value'], d['roofline']['achieved'], d['roofline']['avg_launch_ms'])")
+    (cd $T && python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$T', d['value'], d['roofline']['achieved'], d['roofline']['avg_launch_ms'])")
   done
 done

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 ARGS="${PROF_ARGS:-}"
 STEPS="${PROF_STEPS:-5}"
-BENCH="python $REPO/bench.py --steps $STEPS --warmup 2 --no-cpu-baseline --no-secondary --serial-backward $ARGS"
+BENCH="python $REPO/bench.py --steps $STEPS --warmup 2 --full --no-cpu-baseline --no-secondary --serial-backward $ARGS"
 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench --output-format csv -- $BENCH > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 PMCBENCH="python $REPO/bench.py --steps ${PMC_STEPS:-2} --warmup 1 --no-cpu-baseline --no-secondary --no-prof --serial-backward $ARGS"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA -d "$OUT/pmc_sq" -o bench --output-format csv -- $PMCBENCH > /dev/null 2> "$OUT/pmc_sq.err"

@@ -6,9 +6,9 @@ timeout 600 python scripts/split_numerics.py > $O/numerics_split2h.txt 2>&1; ech
 tail -n 5 $O/numerics_split2h.txt
 timeout 1500 python -m pytest tests/test_unet_gpu.py -q -m gpu -x > $O/unet_split2h.txt 2>&1; echo "unet rc $?"
 tail -n 15 $O/unet_split2h.txt
-timeout 600 python bench.py --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_split2h.json 2> $O/bench_split2h.err; echo "bench rc $?"
+timeout 600 python bench.py --steps 20 --warmup 5 --full --no-secondary --no-cpu-baseline > $O/bench_split2h.json 2> $O/bench_split2h.err; echo "bench rc $?"
 unset RD_MFMA
-timeout 600 python bench.py --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_split3.json 2> $O/bench_split3.err; echo "bench3 rc $?"
+timeout 600 python bench.py --steps 20 --warmup 5 --full --no-secondary --no-cpu-baseline > $O/bench_split3.json 2> $O/bench_split3.err; echo "bench3 rc $?"
 python - <<'PY'
 import json
 for m in ("split2h", "split3"):

@@ -3,8 +3,8 @@
 # CPU baseline, the cfg-G line
 mkdir -p gpurun_out/r06final; O=gpurun_out/r06final
 timeout 1200 python -m pytest tests/test_graph_gpu.py tests/test_plan_gpu.py tests/test_trainer_gpu.py tests/test_engine_state_gpu.py -q -m gpu -x > $O/t.txt 2>&1; echo "tests rc $?"; tail -n 4 $O/t.txt
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
-timeout 600 python bench.py --infer --raster 8192 --steps 2 --warmup 1 > $O/cfgG_bench.json 2> $O/cfgG.err; echo "cfgG rc $?"
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout 600 python bench.py --infer --full --raster 8192 --steps 2 --warmup 1 > $O/cfgG_bench.json 2> $O/cfgG.err; echo "cfgG rc $?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r06final/bench.json").read().strip().splitlines()[-1])

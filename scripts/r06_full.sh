@@ -3,8 +3,8 @@
 mkdir -p gpurun_out/r06b; O=gpurun_out/r06b
 timeout 3000 python -m pytest tests -q -m gpu > $O/gpu_tests.txt 2>&1; echo "tests rc $?"
 tail -n 25 $O/gpu_tests.txt
-timeout 600 python bench.py --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_split2h.json 2> $O/bench_split2h.err; echo "bench rc $?"
-RD_MFMA=split3 timeout 600 python bench.py --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_split3.json 2> $O/bench_split3.err; echo "bench3 rc $?"
+timeout 600 python bench.py --steps 20 --warmup 5 --full --no-secondary --no-cpu-baseline > $O/bench_split2h.json 2> $O/bench_split2h.err; echo "bench rc $?"
+RD_MFMA=split3 timeout 600 python bench.py --steps 20 --warmup 5 --full --no-secondary --no-cpu-baseline > $O/bench_split3.json 2> $O/bench_split3.err; echo "bench3 rc $?"
 python - <<'PY'
 import json
 for m in ("split2h", "split3"):

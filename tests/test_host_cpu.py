@@ -310,3 +310,47 @@ def test_bench_quotes_pmc_traffic_only_from_a_summary_of_the_same_library_and_ar
         assert roof["traffic"] == want, (stamp, roof["traffic"], roof["traffic_source"])
         if want is None:
             assert roof["pmc"] is None and "not quoted" in roof["traffic_source"]
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_long_ones(tmp_path):
+    """bench.py --dump-outputs: every array as DIR/<name>.npy in float32 (float32 sources) or float64, an array longer than its
+    cap as the same seeded sample in every run (sorted indices), and the training dump is what a caller of the step holds."""
+    import importlib
+    import sys
+    import types
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    n32 = bench._dump_array(str(tmp_path), "a", torch.arange(10, dtype=torch.float32), 100)
+    a = np.load(tmp_path / "a.npy")
+    assert a.dtype == np.float32 and n32 == a.nbytes and np.array_equal(a, np.arange(10, dtype=np.float32))
+    bench._dump_array(str(tmp_path), "i", torch.arange(10), 100)
+    assert np.load(tmp_path / "i.npy").dtype == np.float64
+    src = np.arange(100000, dtype=np.float64)
+    draws = []
+    for _ in range(2):
+        bench._dump_array(str(tmp_path), "s", src, 1000)
+        draws.append(np.load(tmp_path / "s.npy"))
+    assert draws[0].dtype == np.float64 and draws[0].shape == (1000,) and np.array_equal(draws[0], draws[1])
+    assert np.all(np.diff(draws[0]) > 0) and draws[0][-1] > 50000         # distinct elements in order, spread over the array
+    bench.dump_infer_outputs(str(tmp_path / "g"), np.ones((64, 48)))
+    assert np.load(tmp_path / "g" / "raster.npy").shape == (64 * 48,)
+    # training: loss of the last step, parameters after its update, BN running statistics, Adam's first moments
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(4, 3), torch.nn.BatchNorm1d(3))
+    opt = torch.optim.Adam(model.parameters(), lr=1e-2)
+    losses = []
+    for _ in range(2):
+        loss = model(torch.randn(8, 4)).square().mean()
+        loss.backward()
+        opt.step()
+        opt.zero_grad()
+        losses.append(loss.detach())
+    bench.dump_train_outputs(str(tmp_path / "t"), types.SimpleNamespace(model=model, opt=opt, losses=losses))
+    out = {n: np.load(tmp_path / "t" / f"{n}.npy") for n in ("loss", "params", "adam_exp_avg", "bn_running_stats")}
+    assert all(v.dtype == np.float32 for v in out.values())
+    assert out["loss"].tolist() == [float(losses[-1])]
+    assert np.array_equal(out["params"], torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy())
+    assert np.array_equal(out["adam_exp_avg"], torch.cat([opt.state[p]["exp_avg"].reshape(-1) for p in model.parameters()]).numpy())
+    bn = model[1]
+    assert np.array_equal(out["bn_running_stats"], torch.cat([bn.running_mean, bn.running_var]).numpy())

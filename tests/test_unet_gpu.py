@@ -611,7 +611,7 @@ def test_bench_gpus_2_runs_end_to_end_without_a_launcher_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["GLOO_SOCKET_IFNAME"] = "lo"
     common = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu"]
-    r = subprocess.run(common + ["--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--no-secondary"],
+    r = subprocess.run(common + ["--steps", "3", "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline", "--no-secondary"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

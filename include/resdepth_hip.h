@@ -475,6 +475,40 @@ size_t rd_residual_stats_ws_bytes(long long n);
 int rd_residual_stats(const double* raster, const float* gt, const uint8_t* mask, long long n, double nodata,
                       double threshold, double* out, void* ws, size_t ws_bytes, rd_stream_t s);
 
+/* ---- class-partitioned evaluation (lib/evaluation.py:163-457 evaluate_performance) --------------------------------- */
+/* out = binary dilation of `in` (nonzero = set) by the L1 ball of radius `iterations` (1..8), out-of-raster pixels unset:
+ * scipy.ndimage.binary_dilation(in, iterations=k) with the default cross structure (lib/rasterutils.py:88 dilate_mask).
+ * One launch; out must not alias in.  Larger radii are chained by the caller. */
+#define RD_DILATE_MAX_ITER 8
+int rd_dilate_mask(const uint8_t* in, uint8_t* out, int rows, int cols, int iterations, rd_stream_t s);
+/* class bits of rd_eval_classify */
+#define RD_CLS_VALID_BEFORE 1  /* gt valid (gt != nodata, gt_mask, inside the area) and initial != nodata */
+#define RD_CLS_VALID_AFTER 2   /* gt valid and prediction != nodata */
+#define RD_CLS_BUILDING 4      /* dilated building mask, inside the area */
+#define RD_CLS_TERRAIN 8       /* !dilated building && !building nodata, inside the area */
+#define RD_CLS_TERRAIN_NOWATER 16
+#define RD_CLS_TERRAIN_NOWATER_NOFOREST 32
+#define RD_EVAL_MAX_RECTS 64
+/* One pass over the rasters of evaluate_performance (lib/evaluation.py:236-359): r_before = initial - gt,
+ * r_after = prediction - gt (fp64; initial and gt are f32 or f64 as flagged, never rounded) and one class byte per
+ * pixel (RD_CLS_*).  gt_mask / building (already dilated) / building_nodata / water / forest are nullable 0/1 bytes;
+ * without `building` no class bit beyond the two valid bits is set.  rects: n_rects half-open [y0, y1, x0, x1) areas
+ * (host array, at most RD_EVAL_MAX_RECTS); n_rects < 0 means the whole raster. */
+int rd_eval_classify(const double* prediction, const void* initial, int initial_f64, const void* gt, int gt_f64,
+                     const uint8_t* gt_mask, const uint8_t* building, const uint8_t* building_nodata,
+                     const uint8_t* water, const uint8_t* forest, const int* rects, int n_rects, int rows, int cols,
+                     double nodata, double* r_before, double* r_after, uint8_t* cls, rd_stream_t s);
+/* Many statistics sets of get_statistics (lib/evaluation.py:50-131) out of one shared set of passes.  Set i takes the
+ * residuals of source set_src[i] (0 -> src0, 1 -> src1) at the pixels whose class byte holds all bits of set_need[i],
+ * dropping |r| > set_thr[i] when set_thr[i] > 0.  out[i*8 .. i*8+7] (device doubles) as rd_residual_stats: count, max,
+ * min, MAE, RMSE, absolute median, median, NMAD; an empty set gives count 0 and NaN elsewhere.  Spec arrays are host
+ * memory; n_sets <= RD_STATS_MAX_SETS. */
+#define RD_STATS_MAX_SETS 20
+size_t rd_residual_stats_sets_ws_bytes(long long n, int n_sets);
+int rd_residual_stats_sets(const double* src0, const double* src1, const uint8_t* cls, long long n, const int* set_src,
+                           const int* set_need, const double* set_thr, int n_sets, double* out, void* ws,
+                           size_t ws_bytes, rd_stream_t s);
+
 /* ---- layout helpers ----------------------------------------------------------------- */
 int rd_nchw_to_nhwc(const float* src, float* dst, int n, int c, int h, int w, rd_stream_t s);
 int rd_nhwc_to_nchw(const float* src, float* dst, int n, int c, int h, int w, rd_stream_t s);

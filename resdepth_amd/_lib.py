@@ -139,6 +139,10 @@ SIGNATURES = {
     "rd_assemble_patches": (I, [P, P, P, LL, P, I, P, P, P, F, P, F, F, I, I, I, P, P, P, P]),
     "rd_residual_stats_ws_bytes": (SZ, [LL]),
     "rd_residual_stats": (I, [P, P, P, LL, D, D, P, P, SZ, P]),
+    "rd_dilate_mask": (I, [P, P, I, I, I, P]),
+    "rd_eval_classify": (I, [P, P, I, P, I, P, P, P, P, P, P, I, I, I, D, P, P, P, P]),
+    "rd_residual_stats_sets_ws_bytes": (SZ, [LL, I]),
+    "rd_residual_stats_sets": (I, [P, P, P, LL, P, P, P, I, P, P, SZ, P]),
     "rd_nchw_to_nhwc": (I, [P, P, I, I, I, I, P]),
     "rd_nhwc_to_nchw": (I, [P, P, I, I, I, I, P]),
     "rd_tune_set": (I, [C.c_char_p, I]),

@@ -202,3 +202,451 @@ int rd_residual_stats(const double* raster, const float* gt, const uint8_t* mask
 }
 
 }  // extern "C"
+
+// ---- class-partitioned evaluation (lib/evaluation.py:163-457 evaluate_performance) -----------------------------------
+// rd_dilate_mask: the L1-ball dilation of lib/rasterutils.py:88 in one launch.  A 64 x 32 output tile is staged in LDS
+// with a k-pixel halo; per haloed row and output column the distance to the nearest set pixel of that row (capped at
+// k + 1), then out = OR over dy of (row distance at dy) <= k - |dy|, exactly the diamond of radius k.
+//
+// rd_residual_stats_sets: every set's moments in one pass (per-set registers, fixed-order block partials), then the
+// exact medians of all sets by the radix select of rd_residual_stats with the histograms of up to SEL_GROUP selectors
+// (set x {median, absolute median} in one phase, NMAD in the next) filled by one read of the residuals per pass.
+
+namespace rd {
+
+constexpr int DIL_TW = 64, DIL_TH = 32;
+constexpr int SEL_GROUP = 20;        // selectors sharing one histogram pass: 20 x 2 ranks x 256 bins x 4 B = 40 KB of LDS
+constexpr int HB = 8;                // pixels per thread and round of the histogram kernel
+
+__global__ __launch_bounds__(256) void dilate_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int rows,
+                                                     int cols, int k) {
+    __shared__ uint8_t tile[(DIL_TH + 2 * RD_DILATE_MAX_ITER) * (DIL_TW + 2 * RD_DILATE_MAX_ITER)];
+    __shared__ uint8_t hd[(DIL_TH + 2 * RD_DILATE_MAX_ITER) * DIL_TW];
+    const int pw = DIL_TW + 2 * k, ph = DIL_TH + 2 * k;
+    const int ox = blockIdx.x * DIL_TW, oy = blockIdx.y * DIL_TH;
+    for (int i = threadIdx.x; i < pw * ph; i += blockDim.x) {
+        const int ty = i / pw, tx = i - ty * pw;
+        const int y = oy - k + ty, x = ox - k + tx;
+        tile[i] = (y >= 0 && y < rows && x >= 0 && x < cols) ? (in[(long)y * cols + x] != 0) : 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < ph * DIL_TW; i += blockDim.x) {
+        const int ty = i / DIL_TW, tx = i - ty * DIL_TW;
+        const uint8_t* c = tile + ty * pw + tx + k;
+        int d = k + 1;
+        for (int dx = k; dx >= 0; --dx)
+            if (c[dx] | c[-dx]) d = dx;
+        hd[i] = (uint8_t)d;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < DIL_TH * DIL_TW; i += blockDim.x) {
+        const int ty = i / DIL_TW, tx = i - ty * DIL_TW;
+        const int y = oy + ty, x = ox + tx;
+        if (y >= rows || x >= cols) continue;
+        bool on = false;
+        for (int dy = -k; dy <= k; ++dy) on |= hd[(ty + k + dy) * DIL_TW + tx] <= k - abs(dy);
+        out[(long)y * cols + x] = on ? 1 : 0;
+    }
+}
+
+struct EvalRects {
+    int n;                               // < 0: the whole raster
+    int r[RD_EVAL_MAX_RECTS][4];         // y0, y1, x0, x1 (half-open)
+};
+
+__device__ __forceinline__ double load_f(const void* p, int f64, long i) {
+    return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i];
+}
+
+__global__ __launch_bounds__(256) void eval_classify_kernel(
+    const double* __restrict__ pred, const void* __restrict__ init, int init_f64, const void* __restrict__ gt, int gt_f64,
+    const uint8_t* __restrict__ gt_mask, const uint8_t* __restrict__ bdil, const uint8_t* __restrict__ bnod,
+    const uint8_t* __restrict__ water, const uint8_t* __restrict__ forest, EvalRects area, int rows, int cols,
+    double nodata, double* __restrict__ rb, double* __restrict__ ra, uint8_t* __restrict__ cls) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= cols) return;
+    for (int y = blockIdx.y; y < rows; y += gridDim.y) {
+        const long i = (long)y * cols + x;
+        bool in = area.n < 0;
+        for (int q = 0; q < area.n; ++q)
+            in |= y >= area.r[q][0] && y < area.r[q][1] && x >= area.r[q][2] && x < area.r[q][3];
+        const double g = load_f(gt, gt_f64, i), a = load_f(init, init_f64, i), p = pred[i];
+        const bool gok = in && g != nodata && (!gt_mask || gt_mask[i]);
+        unsigned c = 0;
+        if (gok && a != nodata) c |= RD_CLS_VALID_BEFORE;
+        if (gok && p != nodata) c |= RD_CLS_VALID_AFTER;
+        if (bdil) {
+            const bool b = bdil[i] != 0;
+            const bool t = in && !b && !(bnod && bnod[i]);
+            const bool tw = t && !(water && water[i]);
+            if (in && b) c |= RD_CLS_BUILDING;
+            if (t) c |= RD_CLS_TERRAIN;
+            if (tw) c |= RD_CLS_TERRAIN_NOWATER;
+            if (tw && !(forest && forest[i])) c |= RD_CLS_TERRAIN_NOWATER_NOFOREST;
+        }
+        rb[i] = a - g;
+        ra[i] = p - g;
+        cls[i] = (uint8_t)c;
+    }
+}
+
+struct SetSpecs {
+    int n;
+    int src[RD_STATS_MAX_SETS];
+    unsigned need[RD_STATS_MAX_SETS];
+    double thr[RD_STATS_MAX_SETS];
+};
+
+__device__ __forceinline__ bool in_set(const SetSpecs& sp, int s, unsigned c, double r) {
+    return (c & sp.need[s]) == sp.need[s] && (sp.thr[s] <= 0.0 || fabs(r) <= sp.thr[s]);
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+// partial[(block * n_sets + s) * 5 + q]: count, sum|r|, sum r^2, min, max of set s over the block's pixels
+__global__ __launch_bounds__(256) void sets_moments_kernel(const double* __restrict__ src0, const double* __restrict__ src1,
+                                                           const uint8_t* __restrict__ cls, long n, SetSpecs sp,
+                                                           double* __restrict__ partial) {
+    double cnt[RD_STATS_MAX_SETS], sa[RD_STATS_MAX_SETS], sq[RD_STATS_MAX_SETS], mn[RD_STATS_MAX_SETS],
+        mx[RD_STATS_MAX_SETS];
+#pragma unroll
+    for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
+        cnt[s] = sa[s] = sq[s] = 0.0;
+        mn[s] = INFINITY;
+        mx[s] = -INFINITY;
+    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const double r0 = src0[i], r1 = src1[i];
+        const unsigned c = cls[i];
+#pragma unroll
+        for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
+            const double d = sp.src[s] ? r1 : r0;
+            if (s < sp.n && in_set(sp, s, c, d)) {
+                cnt[s] += 1.0;
+                sa[s] += fabs(d);
+                sq[s] += d * d;
+                mn[s] = fmin(mn[s], d);
+                mx[s] = fmax(mx[s], d);
+            }
+        }
+    }
+    __shared__ double red[4][5];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
+        if (s >= sp.n) continue;
+        const double v0 = wave_sum(cnt[s]), v1 = wave_sum(sa[s]), v2 = wave_sum(sq[s]), v3 = wave_min(mn[s]),
+                     v4 = wave_max(mx[s]);
+        if (lane == 0) {
+            red[w][0] = v0; red[w][1] = v1; red[w][2] = v2; red[w][3] = v3; red[w][4] = v4;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double* o = partial + ((long)blockIdx.x * sp.n + s) * 5;
+            o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+            o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+            o[2] = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+            o[3] = fmin(fmin(red[0][3], red[1][3]), fmin(red[2][3], red[3][3]));
+            o[4] = fmax(fmax(red[0][4], red[1][4]), fmax(red[2][4], red[3][4]));
+        }
+        __syncthreads();
+    }
+}
+
+// one block per set: fixed-order sum of the block partials (strided per thread, then a fixed tree) -> out[s*8 + 0..4];
+// the selection states of the set's three medians (st[s*3 + mode], mode 0 median, 1 absolute median, 2 NMAD) start
+// from its count
+__global__ __launch_bounds__(256) void sets_moments_finish_kernel(const double* __restrict__ partial, int nb, int n_sets,
+                                                                  double* __restrict__ out, SelState* __restrict__ st) {
+    __shared__ double red[5][256];
+    const int s = blockIdx.x, t = threadIdx.x;
+    double cnt = 0.0, sa = 0.0, sq = 0.0, mn = INFINITY, mx = -INFINITY;
+    for (int b = t; b < nb; b += 256) {
+        const double* p = partial + ((long)b * n_sets + s) * 5;
+        cnt += p[0];
+        sa += p[1];
+        sq += p[2];
+        mn = fmin(mn, p[3]);
+        mx = fmax(mx, p[4]);
+    }
+    red[0][t] = cnt; red[1][t] = sa; red[2][t] = sq; red[3][t] = mn; red[4][t] = mx;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) {
+            red[0][t] += red[0][t + off];
+            red[1][t] += red[1][t + off];
+            red[2][t] += red[2][t + off];
+            red[3][t] = fmin(red[3][t], red[3][t + off]);
+            red[4][t] = fmax(red[4][t], red[4][t + off]);
+        }
+        __syncthreads();
+    }
+    if (t) return;
+    cnt = red[0][0];
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    double* o = out + s * 8;
+    o[0] = cnt;
+    o[1] = cnt > 0 ? red[4][0] : nanv;
+    o[2] = cnt > 0 ? red[3][0] : nanv;
+    o[3] = cnt > 0 ? red[1][0] / cnt : nanv;
+    o[4] = cnt > 0 ? sqrt(red[2][0] / cnt) : nanv;
+    const long long c = (long long)cnt;
+    for (int m = 0; m < 3; ++m) {
+        SelState& q = st[s * 3 + m];
+        q.prefix[0] = q.prefix[1] = 0ull;
+        q.rank[0] = (c - 1) / 2;
+        q.rank[1] = c / 2;
+        q.count = c;
+        q.shift = 0.0;
+    }
+}
+
+// NMAD selections centre on the set's absolute median
+__global__ void sets_shift_kernel(const double* __restrict__ out, int n_sets, SelState* __restrict__ st) {
+    const int s = threadIdx.x;
+    if (s < n_sets) st[s * 3 + 2].shift = out[s * 8 + 5];
+}
+
+struct SelGroup {
+    int n;
+    int set[SEL_GROUP];
+    int mode[SEL_GROUP];
+};
+
+// hist[j*512 + side*256 + bin]: the pass's byte histogram of selector j's values under each of its two prefixes; while the
+// two prefixes agree both ranks read side 0 (the values are counted once)
+__global__ __launch_bounds__(512) void sets_hist_kernel(const double* __restrict__ src0, const double* __restrict__ src1,
+                                                        const uint8_t* __restrict__ cls, long n, SetSpecs sp, SelGroup g,
+                                                        int pass, const SelState* __restrict__ st,
+                                                        unsigned* __restrict__ hist) {
+    __shared__ unsigned lh[SEL_GROUP * 512];
+    __shared__ unsigned long long pf[SEL_GROUP][2];
+    __shared__ double sh[SEL_GROUP];
+    for (int i = threadIdx.x; i < g.n * 512; i += blockDim.x) lh[i] = 0u;
+    if (threadIdx.x < g.n) {
+        const SelState& t = st[g.set[threadIdx.x] * 3 + g.mode[threadIdx.x]];
+        pf[threadIdx.x][0] = t.prefix[0];
+        pf[threadIdx.x][1] = t.prefix[1];
+        sh[threadIdx.x] = t.shift;
+    }
+    __syncthreads();
+    const int hs = 8 * (pass + 1);
+    // HB pixels per thread in registers per round: the selector parameters are read once per round, not per pixel
+    const long step = (long)gridDim.x * blockDim.x * HB;
+    for (long base = (long)blockIdx.x * blockDim.x * HB + threadIdx.x; base < n; base += step) {
+        double r0[HB], r1[HB];
+        int c[HB];
+#pragma unroll
+        for (int u = 0; u < HB; ++u) {
+            const long i = base + (long)u * blockDim.x;
+            const bool ok = i < n;
+            r0[u] = ok ? src0[i] : 0.0;
+            r1[u] = ok ? src1[i] : 0.0;
+            c[u] = ok ? (int)cls[i] : -1;
+        }
+        for (int j = 0; j < g.n; ++j) {
+            const int s = g.set[j], mode = g.mode[j], src = sp.src[s];
+            const int need = (int)sp.need[s];
+            const double thr = sp.thr[s], shift = sh[j];
+            const unsigned long long p0 = pf[j][0], p1 = pf[j][1];
+            unsigned* h = lh + j * 512;
+#pragma unroll
+            for (int u = 0; u < HB; ++u) {
+                const double r = src ? r1[u] : r0[u];
+                if (c[u] < 0 || (c[u] & need) != need || (thr > 0.0 && !(fabs(r) <= thr))) continue;
+                const unsigned long long k = key_of(pick_value(r, mode, shift));
+                const unsigned long long hi = pass == 7 ? 0ull : (k >> hs);
+                const unsigned b = (unsigned)((k >> (8 * pass)) & 255ull);
+                if (hi == p0)
+                    atomicAdd(&h[b], 1u);
+                else if (hi == p1)
+                    atomicAdd(&h[256 + b], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < g.n * 512; i += blockDim.x)
+        if (lh[i]) atomicAdd(&hist[i], lh[i]);
+}
+
+// one block per selector: the bin holding each rank (block-wide inclusive scan), prefixes and ranks advance, the
+// selector's histogram is cleared for the next pass
+__global__ __launch_bounds__(256) void sets_pick_kernel(SelGroup g, SelState* __restrict__ st, unsigned* __restrict__ hist) {
+    __shared__ unsigned long long scan[256];
+    __shared__ int bin_of[2];
+    __shared__ unsigned long long below_of[2];
+    const int j = blockIdx.x, t = threadIdx.x;
+    SelState& S = st[g.set[j] * 3 + g.mode[j]];
+    const bool same = S.prefix[0] == S.prefix[1];
+    unsigned* h = hist + j * 512;
+    for (int side = 0; side < 2; ++side) {
+        const unsigned c = h[(side && !same ? 256 : 0) + t];
+        scan[t] = c;
+        if (t == 0) {
+            bin_of[side] = 255;
+            below_of[side] = 0;
+        }
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const unsigned long long v = t >= o ? scan[t - o] : 0ull;
+            __syncthreads();
+            scan[t] += v;
+            __syncthreads();
+        }
+        const unsigned long long incl = scan[t], excl = incl - c;
+        const unsigned long long rank = (unsigned long long)S.rank[side];
+        if (c && excl <= rank && rank < incl) {
+            bin_of[side] = t;
+            below_of[side] = excl;
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        for (int side = 0; side < 2; ++side) {
+            S.prefix[side] = (S.prefix[side] << 8) | (unsigned long long)bin_of[side];
+            S.rank[side] -= (long long)below_of[side];
+        }
+    }
+    h[t] = 0u;
+    h[256 + t] = 0u;
+}
+
+__global__ void sets_select_finish_kernel(SelGroup g, const SelState* __restrict__ st, double* __restrict__ out) {
+    const int j = threadIdx.x;
+    if (j >= g.n) return;
+    const SelState& S = st[g.set[j] * 3 + g.mode[j]];
+    const int m = g.mode[j];
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    const double scale = m == 2 ? 1.4826 : 1.0;
+    out[g.set[j] * 8 + (m == 1 ? 5 : (m == 0 ? 6 : 7))] =
+        S.count > 0 ? scale * (0.5 * (unkey(S.prefix[0]) + unkey(S.prefix[1]))) : nanv;
+}
+
+__global__ void sets_zero_kernel(unsigned* __restrict__ p, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
+}
+
+static int sets_moment_blocks(long n) {
+    long g = (n + 255) / 256;
+    return (int)(g > 1024 ? 1024 : (g < 1 ? 1 : g));
+}
+static int sets_hist_blocks(long n) {
+    long g = (n + 512 * HB - 1) / (512 * HB);
+    return (int)(g > 1024 ? 1024 : (g < 1 ? 1 : g));
+}
+
+}  // namespace rd
+
+extern "C" {
+
+int rd_dilate_mask(const uint8_t* in, uint8_t* out, int rows, int cols, int iterations, rd_stream_t s_) {
+    RD_REQUIRE(in && out && in != out && rows > 0 && cols > 0, "rd_dilate_mask: bad arguments");
+    RD_REQUIRE(iterations >= 1 && iterations <= RD_DILATE_MAX_ITER, "rd_dilate_mask: iterations %d outside 1..%d",
+               iterations, RD_DILATE_MAX_ITER);
+    hipStream_t s = (hipStream_t)s_;
+    ProfScope ps(s, "dilate_mask", 0, 2.0 * rows * cols);
+    const dim3 grid((cols + DIL_TW - 1) / DIL_TW, (rows + DIL_TH - 1) / DIL_TH);
+    RD_LAUNCH(dilate_kernel, grid, dim3(256), 0, s, in, out, rows, cols, iterations);
+    RD_LAUNCH_CHECK("dilate_mask");
+    return RD_OK;
+}
+
+int rd_eval_classify(const double* prediction, const void* initial, int initial_f64, const void* gt, int gt_f64,
+                     const uint8_t* gt_mask, const uint8_t* building, const uint8_t* building_nodata,
+                     const uint8_t* water, const uint8_t* forest, const int* rects, int n_rects, int rows, int cols,
+                     double nodata, double* r_before, double* r_after, uint8_t* cls, rd_stream_t s_) {
+    RD_REQUIRE(prediction && initial && gt && r_before && r_after && cls && rows > 0 && cols > 0,
+               "rd_eval_classify: bad arguments");
+    RD_REQUIRE(n_rects <= RD_EVAL_MAX_RECTS && (n_rects <= 0 || rects), "rd_eval_classify: %d area rectangles (at most %d)",
+               n_rects, RD_EVAL_MAX_RECTS);
+    EvalRects area;
+    area.n = n_rects;
+    for (int q = 0; q < n_rects; ++q)
+        for (int e = 0; e < 4; ++e) area.r[q][e] = rects[q * 4 + e];
+    hipStream_t s = (hipStream_t)s_;
+    const double n = (double)rows * cols;
+    ProfScope ps(s, "eval_classify", 0, n * (8.0 + (initial_f64 ? 8 : 4) + (gt_f64 ? 8 : 4) + 16.0 + 1.0));
+    const dim3 grid((cols + 255) / 256, rows < 65535 ? rows : 65535);
+    RD_LAUNCH(eval_classify_kernel, grid, dim3(256), 0, s, prediction, initial, initial_f64 ? 1 : 0, gt, gt_f64 ? 1 : 0,
+              gt_mask, building, building_nodata, water, forest, area, rows, cols, nodata, r_before, r_after, cls);
+    RD_LAUNCH_CHECK("eval_classify");
+    return RD_OK;
+}
+
+size_t rd_residual_stats_sets_ws_bytes(long long n, int n_sets) {
+    return (size_t)sets_moment_blocks(n) * RD_STATS_MAX_SETS * 5 * sizeof(double) +
+           (size_t)RD_STATS_MAX_SETS * 3 * sizeof(SelState) + (size_t)SEL_GROUP * 512 * sizeof(unsigned) + 256;
+}
+
+int rd_residual_stats_sets(const double* src0, const double* src1, const uint8_t* cls, long long n, const int* set_src,
+                           const int* set_need, const double* set_thr, int n_sets, double* out, void* ws,
+                           size_t ws_bytes, rd_stream_t s_) {
+    RD_REQUIRE(src0 && cls && out && n > 0 && set_src && set_need && set_thr, "rd_residual_stats_sets: bad arguments");
+    RD_REQUIRE(n_sets >= 1 && n_sets <= RD_STATS_MAX_SETS, "rd_residual_stats_sets: %d sets (1..%d)", n_sets,
+               RD_STATS_MAX_SETS);
+    if (!ws || ws_bytes < rd_residual_stats_sets_ws_bytes(n, n_sets)) {
+        set_error("rd_residual_stats_sets: workspace too small (%zu < %zu)", ws_bytes,
+                  rd_residual_stats_sets_ws_bytes(n, n_sets));
+        return RD_ERR_WS;
+    }
+    SetSpecs sp;
+    sp.n = n_sets;
+    for (int i = 0; i < RD_STATS_MAX_SETS; ++i) {
+        sp.src[i] = i < n_sets ? set_src[i] : 0;
+        sp.need[i] = i < n_sets ? (unsigned)set_need[i] : 0u;
+        sp.thr[i] = i < n_sets ? set_thr[i] : -1.0;
+        RD_REQUIRE(sp.src[i] == 0 || (sp.src[i] == 1 && src1), "rd_residual_stats_sets: set %d reads source %d", i,
+                   sp.src[i]);
+    }
+    if (!src1) src1 = src0;
+    hipStream_t s = (hipStream_t)s_;
+    const int nbm = sets_moment_blocks(n), nbh = sets_hist_blocks(n);
+    char* base = (char*)ws;
+    double* partial = (double*)base;
+    SelState* st = (SelState*)(base + (size_t)nbm * RD_STATS_MAX_SETS * 5 * sizeof(double));
+    unsigned* hist = (unsigned*)((char*)st + (size_t)RD_STATS_MAX_SETS * 3 * sizeof(SelState));
+    // selectors: every set's median and absolute median (phase 0), then every set's NMAD (phase 1), SEL_GROUP per pass
+    SelGroup groups[3 * RD_STATS_MAX_SETS / SEL_GROUP + 3];
+    int phase_end[2] = {0, 0}, ng = 0;
+    for (int phase = 0; phase < 2; ++phase) {
+        const int nsel = phase == 0 ? 2 * n_sets : n_sets;
+        for (int j0 = 0; j0 < nsel; j0 += SEL_GROUP) {
+            SelGroup& g = groups[ng++];
+            g.n = nsel - j0 < SEL_GROUP ? nsel - j0 : SEL_GROUP;
+            for (int j = 0; j < SEL_GROUP; ++j) {
+                const int q = j0 + (j < g.n ? j : 0);
+                g.set[j] = phase == 0 ? q >> 1 : q;
+                g.mode[j] = phase == 0 ? (q & 1) : 2;
+            }
+        }
+        phase_end[phase] = ng;
+    }
+    ProfScope ps(s, "residual_stats_sets", 0, 17.0 * n * (1 + 8 * ng));
+    RD_LAUNCH(sets_zero_kernel, dim3(1), dim3(256), 0, s, hist, SEL_GROUP * 512);
+    RD_LAUNCH(sets_moments_kernel, dim3(nbm), dim3(256), 0, s, src0, src1, cls, (long)n, sp, partial);
+    RD_LAUNCH(sets_moments_finish_kernel, dim3(n_sets), dim3(256), 0, s, (const double*)partial, nbm, n_sets, out, st);
+    for (int gi = 0; gi < ng; ++gi) {
+        if (gi == phase_end[0]) RD_LAUNCH(sets_shift_kernel, dim3(1), dim3(64), 0, s, (const double*)out, n_sets, st);
+        for (int pass = 7; pass >= 0; --pass) {
+            RD_LAUNCH(sets_hist_kernel, dim3(nbh), dim3(512), 0, s, src0, src1, cls, (long)n, sp, groups[gi], pass,
+                      (const SelState*)st, hist);
+            RD_LAUNCH(sets_pick_kernel, dim3(groups[gi].n), dim3(256), 0, s, groups[gi], st, hist);
+        }
+        RD_LAUNCH(sets_select_finish_kernel, dim3(1), dim3(64), 0, s, groups[gi], (const SelState*)st, out);
+    }
+    RD_LAUNCH_CHECK("residual_stats_sets");
+    return RD_OK;
+}
+
+}  // extern "C"

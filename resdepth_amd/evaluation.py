@@ -3,6 +3,10 @@
 numpy masked arrays and three full sorts on the CPU).  Returns the reference's statistic names as python floats."""
 from __future__ import annotations
 
+import ctypes
+import logging
+import os
+
 import numpy as np
 import torch
 
@@ -43,3 +47,360 @@ def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=N
         stats["truncated"] = {"count_total": tv[0], "threshold": residual_threshold, "MAE": tv[3], "RMSE": tv[4],
                               "absolute_median": tv[5], "median": tv[6], "NMAD": tv[7]}
     return stats
+
+
+# ---- class-partitioned evaluation (lib/evaluation.py:134-457: print_statistics, evaluate_performance) ----------------
+VALID_BEFORE, VALID_AFTER = 1, 2                      # class bits of rd_eval_classify (include/resdepth_hip.h RD_CLS_*)
+CLASS_BITS = {"all": 0, "building": 4, "terrain": 8, "terrain_nowater": 16, "terrain_nowater_noforest": 32}
+MAX_SETS = 20                                         # RD_STATS_MAX_SETS
+MAX_DILATE = 8                                        # RD_DILATE_MAX_ITER: larger radii chain launches
+
+
+class AttrDict(dict):
+    """dict with attribute access (the reference's EasyDict): `stats.MAE`, `residuals.all`."""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError:
+            raise AttributeError(k) from None
+
+    __setattr__ = dict.__setitem__
+
+
+def _device(dev):
+    dev = torch.device(dev)
+    if dev.type != "cuda":
+        raise RuntimeError("resdepth_amd.evaluation needs a HIP device (no CPU fallback)")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _on(x, dev, dtype=None):
+    """numpy array / tensor -> contiguous tensor on `dev` (dtype kept unless given)."""
+    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+    return t.to(dev, dtype).contiguous() if dtype is not None else t.to(dev).contiguous()
+
+
+def _dilate_u8(m, iterations):
+    """uint8 0/1 device raster -> dilated uint8 0/1 raster (rd_dilate_mask, radius chained in steps of <= 8)."""
+    rows, cols = m.shape
+    lib = load()
+    with torch.cuda.device(m.device):
+        while iterations > 0:
+            k = min(iterations, MAX_DILATE)
+            out = torch.empty_like(m)
+            check(lib.rd_dilate_mask(ptr(m), ptr(out), rows, cols, k, stream_ptr()), "dilate_mask")
+            m, iterations = out, iterations - k
+    return m
+
+
+def dilate_mask(mask, iterations=1, device="cuda"):
+    """GPU counterpart of lib/rasterutils.py:88 dilate_mask: scipy.ndimage.binary_dilation(mask, iterations=k) with the
+    default cross structure (the L1 ball of radius k; pixels outside the raster count as unset), k >= 1.  Takes a 2-D
+    numpy array or tensor (nonzero = set) and returns the same kind: a bool ndarray, or a bool tensor on the input's
+    device."""
+    iterations = int(iterations)
+    if iterations < 1:
+        raise ValueError(f"dilate_mask: iterations must be >= 1 (got {iterations})")
+    if len(mask.shape) != 2 or min(mask.shape) == 0:
+        raise ValueError(f"dilate_mask: expected a non-empty 2-D raster, got shape {tuple(mask.shape)}")
+    dev = _device(mask.device if torch.is_tensor(mask) and mask.is_cuda else device)
+    m = _on(mask, dev)
+    m = (m != 0).to(torch.uint8).contiguous()
+    out = _dilate_u8(m, iterations).bool()
+    if torch.is_tensor(mask):
+        return out.to(mask.device)
+    return out.cpu().numpy()
+
+
+def _mask_pair(spec, dev):
+    """A mask argument -> (mask, nodata_mask) uint8 device rasters, converted like lib/rasterutils.py:23
+    load_mask_raster: set where the value is 1 and not the nodata value.  `spec`: an array / tensor, a
+    (values, nodata) tuple or a dataset-like object (ReadAsArray(), GetRasterBand(1).GetNoDataValue())."""
+    if hasattr(spec, "ReadAsArray"):
+        values, nd = spec.ReadAsArray(), spec.GetRasterBand(1).GetNoDataValue()
+    elif isinstance(spec, tuple):
+        values, nd = spec
+    else:
+        values, nd = spec, None
+    v = _on(values, dev)
+    if v.dtype == torch.bool:
+        v = v.to(torch.uint8)
+    nodata = torch.zeros(v.shape, dtype=torch.bool, device=dev) if nd is None else (v == nd)
+    return ((v == 1) & ~nodata).to(torch.uint8).contiguous(), nodata.to(torch.uint8).contiguous()
+
+
+def _rects(area_defn, rows, cols):
+    """area_defn (inclusive x / y extents per stripe) -> half-open [y0, y1, x0, x1) rows, numpy slicing semantics."""
+    if area_defn is None:
+        return None
+    out = []
+    for x, y in zip(area_defn["x_extent"], area_defn["y_extent"]):
+        y0, y1, _ = slice(int(y[0]), int(y[1]) + 1).indices(rows)
+        x0, x1, _ = slice(int(x[0]), int(x[1]) + 1).indices(cols)
+        out.append((y0, max(y0, y1), x0, max(x0, x1)))
+    return out
+
+
+def _run_sets(src0, src1, cls, sets, dev):
+    """sets: [(source, need bits, threshold or None)] -> host float64 array [len(sets), 8] (rd_residual_stats_sets)."""
+    n = cls.numel()
+    ns = len(sets)
+    lib = load()
+    src_a = (ctypes.c_int * ns)(*[s for s, _, _ in sets])
+    need_a = (ctypes.c_int * ns)(*[b for _, b, _ in sets])
+    thr_a = (ctypes.c_double * ns)(*[float(t) if t else -1.0 for _, _, t in sets])
+    out = torch.empty((ns, 8), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.rd_residual_stats_sets_ws_bytes(n, ns), dev, slot=3)
+        check(lib.rd_residual_stats_sets(ptr(src0), ptr(src1), ptr(cls), n, src_a, need_a, thr_a, ns, ptr(out),
+                                         ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats_sets")
+        return out.cpu().numpy()
+
+
+def _stats_dict(full, trunc, thr):
+    """rows of rd_residual_stats_sets -> the reference's get_statistics dict."""
+    st = AttrDict(truncation=bool(thr))
+    if thr:
+        st.truncated = AttrDict(count_total=float(trunc[0]), threshold=thr, MAE=float(trunc[3]), RMSE=float(trunc[4]),
+                                absolute_median=float(trunc[5]), median=float(trunc[6]), NMAD=float(trunc[7]))
+    st.update(zip(_KEYS, (float(v) for v in full)))
+    return st
+
+
+def _float_raster(x, dev):
+    """DSM as given when f32 / f64 (never rounded), anything else as f64."""
+    t = _on(x, dev)
+    return t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float64)
+
+
+def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
+              nodata, dev):
+    """-> (stats {'before', 'after'}, r_after, cls, classes) with r_after / cls on the device."""
+    pred = _on(prediction, dev, torch.float64)
+    init, g = _float_raster(initial, dev), _float_raster(gt, dev)
+    if pred.dim() != 2 or pred.shape != init.shape or pred.shape != g.shape:
+        raise ValueError(f"evaluate: prediction {tuple(pred.shape)}, initial {tuple(init.shape)} and ground truth "
+                         f"{tuple(g.shape)} must be equal 2-D rasters")
+    rows, cols = pred.shape
+    gm = None if mask_gt is None else _mask_pair(mask_gt, dev)[0]
+    bdil = bnod = water = forest = None
+    classes = ["all"]
+    if mask_building is not None:
+        b, bnod = _mask_pair(mask_building, dev)
+        bdil = _dilate_u8(b, 2)                        # lib/evaluation.py:282: dilated on the whole raster
+        classes += ["building", "terrain"]
+        if mask_water is not None:
+            water = _mask_pair(mask_water, dev)[0]
+            classes.append("terrain_nowater")
+        if mask_forest is not None:
+            forest = _mask_pair(mask_forest, dev)[0]
+            classes.append("terrain_nowater_noforest")
+    for name, m in (("gt mask", gm), ("building mask", bdil), ("water mask", water), ("forest mask", forest)):
+        if m is not None and tuple(m.shape) != (rows, cols):
+            raise ValueError(f"evaluate: {name} shape {tuple(m.shape)} != raster shape {(rows, cols)}")
+    rects = _rects(area_defn, rows, cols)
+    rect_a = None if rects is None else (ctypes.c_int * (4 * max(len(rects), 1)))(*[v for r in rects for v in r])
+    nd = float("nan") if nodata is None else float(nodata)
+    r_before = torch.empty((rows, cols), dtype=torch.float64, device=dev)
+    r_after = torch.empty_like(r_before)
+    cls = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    lib = load()
+    with torch.cuda.device(dev):
+        check(lib.rd_eval_classify(ptr(pred), ptr(init), int(init.dtype == torch.float64), ptr(g),
+                                   int(g.dtype == torch.float64), ptr(gm), ptr(bdil), ptr(bnod), ptr(water), ptr(forest),
+                                   rect_a, -1 if rects is None else len(rects), rows, cols, nd, ptr(r_before),
+                                   ptr(r_after), ptr(cls), stream_ptr()), "eval_classify")
+    sets = []
+    for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)):
+        for c in classes:
+            sets.append((src, valid | CLASS_BITS[c], None))
+            if residual_threshold:
+                sets.append((src, valid | CLASS_BITS[c], residual_threshold))
+    res = _run_sets(r_before, r_after, cls, sets, dev)
+    stats = AttrDict(before=AttrDict(), after=AttrDict())
+    step = 2 if residual_threshold else 1
+    for q, (src, need, _) in enumerate(sets[::step]):
+        c = classes[q % len(classes)]
+        row = q * step
+        stats["after" if src else "before"][c] = _stats_dict(res[row], res[row + 1] if step == 2 else None,
+                                                             residual_threshold)
+    return stats, r_after, cls, classes
+
+
+def evaluate_statistics(prediction, initial, gt, area_defn=None, mask_gt=None, mask_building=None, mask_water=None,
+                        mask_forest=None, residual_threshold=None, *, nodata=None, device="cuda"):
+    """The statistics of lib/evaluation.py:163-457 evaluate_performance on the GPU: one classification pass, then every
+    statistics set (initial / refined DSM x all / building / terrain / terrain without water / terrain without water and
+    forest, each with its truncated variant) out of one shared set of radix-select passes.
+
+    prediction: refined DSM; initial: initial DSM; gt: ground-truth DSM (numpy arrays or tensors; f32 / f64 DSMs are
+    read as given).  nodata: the ground truth's nodata value (None: none).  Masks: arrays / tensors (value 1 = set),
+    (values, nodata) tuples or dataset-like objects; water and forest only count with a building mask.
+    -> {'before': {class: stats}, 'after': {class: stats}} in the reference's get_statistics format, attribute access."""
+    dev = None
+    for x in (prediction, initial, gt):
+        if torch.is_tensor(x) and x.is_cuda:
+            dev = x.device
+            break
+    dev = _device(dev if dev is not None else device)
+    return _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest,
+                     residual_threshold, nodata, dev)[0]
+
+
+def print_statistics(stats, logger, print_min_max=True):
+    """The report block of lib/evaluation.py:134-160, line for line."""
+    if print_min_max:
+        logger.info("Maximum residual error [m]:\t\t\t\t\t\t{:10.3f} m".format(stats.diff_max))
+        logger.info("Minimum residual error [m]:\t\t\t\t\t\t{:10.3f} m".format(stats.diff_min))
+    logger.info("Mean absolute residual error (MAE) [m]:\t\t\t\t\t{:10.3f} m".format(stats.MAE))
+    logger.info("RMSE residual error [m]:\t\t\t\t\t\t{:10.3f} m".format(stats.RMSE))
+    logger.info("Absolute median residual error [m]:\t\t\t\t\t{:10.3f} m".format(stats.absolute_median))
+    logger.info("Median residual error [m]:\t\t\t\t\t\t{:10.3f} m".format(stats.median))
+    logger.info("Normalized median absolute deviation (NMAD) [m]:\t\t\t{:10.3f} m\n".format(stats.NMAD))
+    if stats.truncation:
+        t = stats.truncated
+        logger.info("Truncated mean absolute residual error (MAE) [m]:\t\t\t{:10.3f} m".format(t.MAE))
+        logger.info("Truncated RMSE residual error [m]:\t\t\t\t\t{:10.3f} m".format(t.RMSE))
+        logger.info("Truncated absolute median residual error [m]:\t\t\t\t{:10.3f} m".format(t.absolute_median))
+        logger.info("Truncated median residual error [m]:\t\t\t\t\t{:10.3f} m".format(t.median))
+        logger.info("Truncated normalized median absolute deviation (NMAD) [m]:\t\t{:10.3f} m\n".format(t.NMAD))
+
+
+def _gdal():
+    try:
+        from osgeo import gdal
+    except ImportError as e:
+        raise ImportError("resdepth_amd.evaluation: opening a raster from a path needs GDAL (osgeo.gdal), which is not "
+                          "installed; pass arrays or opened datasets instead") from e
+    return gdal
+
+
+def _open(path):
+    ds = _gdal().Open(path, 0)
+    if ds is None:
+        raise ValueError("Could not open {}".format(path))
+    return ds
+
+
+def _mask_arg(arg, what, logger_root):
+    """A mask argument of evaluate_performance -> something _mask_pair takes, or None (absent / missing file)."""
+    if arg is None or (isinstance(arg, str) and not arg):
+        return None
+    if isinstance(arg, str):
+        if not os.path.exists(arg):
+            logger_root.info("Cannot find the {}: {}".format(what, arg))
+            return False
+        logger_root.info("\tLoad the {}...".format(what))
+        return _open(arg)
+    return arg
+
+
+# (class, report heading) in the reference's report order; the forest heading depends on whether water was given
+_HEADINGS = {"all": "OVERALL", "building": "BUILDING PIXELS", "terrain": "TERRAIN PIXELS",
+             "terrain_nowater": "TERRAIN PIXELS WITHOUT WATER",
+             "terrain_nowater_noforest": ("TERRAIN PIXELS WITHOUT WATER/FOREST", "TERRAIN PIXELS WITHOUT FOREST")}
+
+
+def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logger_root, area_defn=None,
+                         path_gt_mask=None, path_building_mask=None, path_water_mask=None, path_forest_mask=None,
+                         logger_stats=None, residual_threshold=None, *, nodata=None, gsd=None, device="cuda"):
+    """Drop-in for lib/evaluation.py:163 evaluate_performance: the same report on `logger_stats` and the same return
+    value, the attribute dict `residuals.after` of host np.ma.MaskedArrays (class -> residuals of the refined DSM).
+
+    The DSMs are arrays / tensors or dataset-like objects (GetRasterBand(1).ReadAsArray(), GetNoDataValue(),
+    GetGeoTransform()); for arrays the ground truth's nodata value and the GSD come from `nodata=` / `gsd=`.  Mask
+    arguments: arrays (value 1 = set), (values, nodata) tuples, dataset-like objects or paths (paths need osgeo.gdal; a
+    path that does not exist is logged and skipped; a missing ground-truth mask means all ground-truth pixels)."""
+    if logger_stats is None:
+        logger_stats = logging.getLogger("stats_logger")
+        logger_stats.setLevel(logging.INFO)
+        if not logger_stats.handlers:
+            logger_stats.addHandler(logging.StreamHandler())
+
+    def raster(x, what):
+        if isinstance(x, str):
+            logger_root.info("\tLoad the {}...".format(what))
+            x = _open(x)
+        return (x.GetRasterBand(1).ReadAsArray(), x) if hasattr(x, "GetRasterBand") else (x, None)
+
+    pred, _ = raster(raster_prediction, "refined DSM")
+    gt, ds_gt = raster(ds_raster_gt, "ground truth DSM")
+    init, ds_in = raster(ds_raster_input, "initial DSM")
+    if ds_gt is not None:
+        nodata = ds_gt.GetRasterBand(1).GetNoDataValue()
+    if ds_in is not None:
+        gsd = ds_in.GetGeoTransform()[1]
+    if gsd is None:
+        raise ValueError("evaluate_performance: pass gsd= when the initial DSM is an array")
+
+    mask_gt = _mask_arg(path_gt_mask, "ground truth mask", logger_root)
+    if mask_gt is False:
+        logger_root.info("Evaluating the performance by using all ground truth DSM pixels with a valid height.")
+        mask_gt = None
+    mask_b = _mask_arg(path_building_mask, "building mask", logger_root)
+    mask_w = mask_f = None
+    if mask_b is False:
+        logger_root.info("Evaluating the performance over all pixels.")
+        mask_b = None
+    if path_building_mask is not None and not (isinstance(path_building_mask, str) and not path_building_mask):
+        # the reference reads the water / forest masks only under a building mask
+        mask_w = _mask_arg(path_water_mask, "water mask", logger_root)
+        if mask_w is False:
+            logger_root.info("Evaluating the performance without excluding water pixels.")
+            mask_w = None
+        mask_f = _mask_arg(path_forest_mask, "forest mask", logger_root)
+        if mask_f is False:
+            logger_root.info("Evaluating the performance without excluding forest pixels.")
+            mask_f = None
+
+    dev = _device(device)
+    logger_root.info("\tCompute residual errors and statistics before and after the refinement...")
+    stats, r_after, cls, classes = _evaluate(pred, init, gt, area_defn, mask_gt, mask_b, mask_w, mask_f,
+                                             residual_threshold, nodata, dev)
+
+    area_size = float(stats.before.all["count_total"] * gsd * gsd) / 1000000
+    logger_stats.info("\n\nPerformance Evaluation\n----------------------\n")
+    logger_stats.info("Number of pixels:\t\t\t{}".format(int(stats.before.all["count_total"])))
+    logger_stats.info("Area [km^2]:\t\t\t\t{:.2f}\n".format(area_size))
+    if residual_threshold:
+        logger_stats.info("Truncation threshold:\t\t\t{:.2f} m\n".format(residual_threshold))
+    for c in classes:
+        head = _HEADINGS[c]
+        if isinstance(head, tuple):
+            head = head[0] if "terrain_nowater" in classes else head[1]
+        for when, dsm in (("before", "INITIAL"), ("after", "REFINED")):
+            title = "STATISTICS, {}: {} DSM".format(head, dsm)
+            rule = len(title) + (c == "all" and when == "before")     # the reference's first rule is one dash longer
+            logger_stats.info("\n{}\n{}\n".format(title, "-" * rule))
+            print_statistics(stats[when][c], logger_stats)
+
+    data = r_after.cpu().numpy()
+    bits = cls.cpu().numpy()
+    valid = (bits & VALID_AFTER) != 0
+    residuals = AttrDict()
+    for c in classes:
+        ok = valid if c == "all" else valid & ((bits & CLASS_BITS[c]) != 0)
+        residuals[c] = np.ma.MaskedArray(data, mask=~ok, copy=False)
+    return residuals
+
+
+def get_statistics_masked(residuals_masked, residual_threshold=None, device="cuda"):
+    """The reference's get_statistics(residuals_masked, residual_threshold) (lib/evaluation.py:50): statistics of the
+    unmasked values of an np.ma array (or of every value of an ndarray / tensor), any shape -- e.g. residuals pooled
+    over several image pairs as in test.py.  -> the reference's statistics dict (attribute access)."""
+    if torch.is_tensor(residuals_masked):
+        dev = _device(residuals_masked.device if residuals_masked.is_cuda else device)
+        r = residuals_masked.to(dev, torch.float64).reshape(-1).contiguous()
+        valid = torch.ones(r.shape, dtype=torch.uint8, device=dev)
+    else:
+        dev = _device(device)
+        a = np.ma.asarray(residuals_masked)
+        r = _on(np.ma.getdata(a).astype(np.float64, copy=False).reshape(-1), dev)
+        valid = _on((~np.ma.getmaskarray(a)).reshape(-1).astype(np.uint8), dev)
+    if r.numel() == 0:                                 # nothing to read: the statistics of an empty set
+        r = torch.zeros(1, dtype=torch.float64, device=dev)
+        valid = torch.zeros(1, dtype=torch.uint8, device=dev)
+    sets = [(0, 1, None)] + ([(0, 1, residual_threshold)] if residual_threshold else [])
+    res = _run_sets(r, None, valid, sets, dev)
+    return _stats_dict(res[0], res[1] if residual_threshold else None, residual_threshold)

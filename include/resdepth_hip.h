@@ -56,8 +56,15 @@ int rd_mfma_products(void);
  * producer runs: sixteen 32-bit words, one at the start of each 128-byte line (same-line device atomics serialise; sixteen
  * lines take them in parallel).  The producer max-accumulates the IEEE bit patterns of |x| into them (atomic integer max:
  * order-independent, so run-to-run identical) and a consumer takes the largest of the 16 words as the tensor's maximum.
+ * Word 1 of each line (library 108): the producer blocks with a non-zero maximum m max-accumulate ~bits(m) into it, so the slot
+ * also holds the smallest non-zero block maximum; a consumer runs the six-product body when max > 2^17 x that (an operand with a
+ * block of values far below the largest element elsewhere in the tensor: a batch mate, an image region).  Every producer block
+ * covers a contiguous range of its tensor.  Bound per product for an ARBITRARY tensor pair: |ab - q(a)q(b)| <= 3 * 2^-22 |ab|
+ * + 2^-39 (amax(a) |b| + amax(b) |a|); the guard keeps whole blocks near the first term, but values small next to others in their
+ * own block -- e.g. a few channels of small magnitude, which every block holds -- are bounded by the second only.
  *   rd_quant_next(a, b, out, out2): the slots the NEXT rd_* call of this host thread takes (any may be NULL); that call clears
- *     them again, whether it uses them or not.  Consumers (rd_conv3x3_fwd*, rd_conv3x3_bwd_data*, rd_convt2x2_fwd*,
+ *     them again, whether it uses them or not -- also when it fails its argument checks.  Consumers (rd_conv3x3_fwd*,
+ *     rd_conv3x3_bwd_data*, rd_convt2x2_fwd*,
  *     rd_convt2x2_bwd_data*, rd_conv1x1_*): a = slot of the activation / gradient operand, b = slot of the packed weight;
  *     weight gradients (rd_*_bwd_weight): a = slot of the gradient operand (dz / dout / dy), b = slot of x.  Producers: out =
  *     slot that receives max |primary output| (z is not an operand and gets none: rd_conv3x3_fwd_act -> a, rd_conv3x3_bwd_data*

@@ -208,6 +208,27 @@ def products() -> int:
 # and backward), consumers read the attribute -- a tensor without one (any torch op's result, a view, .contiguous()) simply
 # runs the six-product body.
 _tls = threading.local()
+_pool_log = None          # a list: every AmaxPool created while it is set is appended to it (tests inspect what a pass wrote)
+GUARD_EXP = 17            # csrc/rd_mfma_dev.h: three products only while max <= 2^GUARD_EXP x the smallest non-zero block maximum
+
+
+def slot_decode(words):
+    """Host view of one magnitude slot (RD_AMAX_SLOT_BYTES as int32, any array-like): (maximum, smallest non-zero block maximum)
+    as floats.  Word 0 of each of the sixteen 128-byte lines: max of |x| bit patterns; word 1: max of ~bits(block maximum) over
+    the producer blocks with a non-zero maximum.  (0.0, None) = a slot nobody wrote; min is None when no block reported one."""
+    import numpy as np
+    w = np.asarray(words, dtype=np.int64).reshape(16, 32) & 0xFFFFFFFF
+    top = int(w[:, 0].max())
+    low = int(w[:, 1].max())
+    f = lambda b: float(np.array([b], dtype=np.uint32).view(np.float32)[0])
+    return f(top), (f(~low & 0xFFFFFFFF) if low else None)
+
+
+def slot_takes_three_products(words) -> bool:
+    """quant_select's decision for one operand slot: written, finite maximum, and the block maxima within 2^GUARD_EXP."""
+    import math
+    top, low = slot_decode(words)
+    return top != 0.0 and math.isfinite(top) and low is not None and top <= low * 2.0 ** GUARD_EXP
 
 
 class AmaxPool:
@@ -220,6 +241,8 @@ class AmaxPool:
         self.words = AMAX_WORDS * max(1, self.img)
         self.buf = zeros_i32(slots * self.words, device)
         self.n, self.cap = 0, slots
+        if _pool_log is not None:
+            _pool_log.append(self)
 
     def take(self):
         if self.n >= self.cap:

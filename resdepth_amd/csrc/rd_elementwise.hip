@@ -379,7 +379,9 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const float* __res
     const float slope = slope_dev ? slope_dev[0] : slope_val;   // PReLU: learnable slope read on the device
     const long total = rows * CQ;
     float amx = 0.f, pmx = 0.f;     // a_amax / p_amax (nullable): magnitude slots of a / pooled (operands of three-product GEMMs)
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    long e0, e1;      // a contiguous share per block (not a grid-stride walk): the slots' block maxima stay local
+    block_range(total, blockIdx.x, gridDim.x, blockDim.x, e0, e1);
+    for (long e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
         const int cq = (int)(e % CQ);
         const long row = e / CQ;
         const float4 mu = *reinterpret_cast<const float4*>(mean + cq * 4);

@@ -698,11 +698,14 @@ __device__ __forceinline__ float pack_scale_wave(const unsigned* amax) {  // eve
     return __uint_as_float((unsigned)scale_bexp(amax_read_wave(amax)) << 23);
 }
 
-// max |w| of weight tensors into their magnitude slots: block b of an item strides over the item's elements
+// max |w| of a tensor into its magnitude slot: block b walks a contiguous share of the elements (block maxima are local: the
+// guard of quant_select)
 __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ w, long n, unsigned* slot, const float* __restrict__ row_scale,
                                                    long row_len) {
     float m = 0.f;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x)
+    long e0, e1;
+    block_range(n, blockIdx.x, gridDim.x, blockDim.x, e0, e1);
+    for (long e = e0 + threadIdx.x; e < e1; e += blockDim.x)
         m = amax_acc(m, row_scale ? w[e] * row_scale[e / row_len] : w[e]);
     amax_commit(slot, m);
 }
@@ -858,13 +861,16 @@ __global__ __launch_bounds__(256) void pack_items_amax_kernel(const PackItem* __
     const float* __restrict__ w = reinterpret_cast<const float*>(I.w);
     const long n = (long)I.cout * I.cin * (I.kind == 0 ? 9 : 4);
     float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
-    const long stride = (long)AMAX_PARTS * 256;
-    long e = (long)part * 256 + threadIdx.x;
-    for (; e + 3 * stride < n; e += 4 * stride) {
+    // a contiguous share of the item per block (local block maxima: the guard of quant_select), 256-element steps
+    long e0, e1;
+    block_range(n, part, AMAX_PARTS, 256, e0, e1);
+    constexpr long stride = 256;
+    long e = e0 + threadIdx.x;
+    for (; e + 3 * stride < e1; e += 4 * stride) {
         const float a = w[e], b = w[e + stride], c = w[e + 2 * stride], d = w[e + 3 * stride];
         m0 = amax_acc(m0, a); m1 = amax_acc(m1, b); m2 = amax_acc(m2, c); m3 = amax_acc(m3, d);
     }
-    for (; e < n; e += stride) m0 = amax_acc(m0, w[e]);
+    for (; e < e1; e += stride) m0 = amax_acc(m0, w[e]);
     amax_commit(reinterpret_cast<unsigned*>(I.amax), fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)));
 }
 

@@ -50,7 +50,8 @@ constexpr int SROWB3 = 64;  // ... three-product form (2 fp16 terms), which foll
 //          elements within 2^-18 of their tensor's maximum (64 x tighter than two bf16 terms), and <= 2^-39 amax(a) |b| below.
 //          It needs the tensor maxima: producers max-accumulate |x| into a 16-word device slot from their epilogues
 //          (amax_commit; an integer max of IEEE bit patterns is order-independent, so results stay run-to-run identical) and
-//          the consumer reads them at kernel start (quant_select).  An operand without a slot, or whose maximum is Inf (NaN
+//          the consumer reads them at kernel start (quant_select).  An operand without a slot, whose block maxima span more than
+//          2^17 (the guard, see GUARD_EXP), or whose maximum is Inf (NaN
 //          elements are fine: they stay NaN in both terms), sends the launch to the NP = 6 body -- which therefore keeps
 //          fp32's non-finite semantics.
 // =====================================================================================================================
@@ -99,12 +100,39 @@ __device__ __forceinline__ int scale_bexp(unsigned am) {
     const int b = 268 - (int)(am >> 23);
     return b > 254 ? 254 : b;
 }
+// the guard (r07): word 1 of every line holds the atomic max of ~bits(block maximum) over the producer blocks whose maximum is
+// non-zero, i.e. the complement of the SMALLEST non-zero block maximum.  A tensor whose largest element exceeds 2^17 x that
+// (a block of small values beside a large one elsewhere: a batch mate of another magnitude, a region of the image) would have
+// elements below 2^-18 of the scale's range -- their second fp16 term subnormal, 2^-9-class products -- and goes to NP = 6.
+constexpr int GUARD_EXP = 17;
+// both slot words with ONE load: lanes 0..15 fetch word 0 of line `lane` (maximum), lanes 16..31 word 1 of line `lane - 16`
+// (complement of the smallest block maximum); the maximum of each 16-lane group by cross-lane exchange.  m = word-0 maximum,
+// nb = word-1 maximum (0: no block with a non-zero maximum committed).
+__device__ __forceinline__ void amax_read_wave2(const unsigned* __restrict__ slot, unsigned& m, unsigned& nb) {
+    const int lane = threadIdx.x & 63;
+    unsigned v = lane < 2 * AMAX_WORDS ? slot[(lane & (AMAX_WORDS - 1)) * AMAX_STRIDE + (lane >> 4)] : 0u;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+        const unsigned other = (unsigned)__shfl_xor((int)v, o);
+        v = other > v ? other : v;
+    }
+    m = (unsigned)__builtin_amdgcn_readlane((int)v, 0);
+    nb = (unsigned)__builtin_amdgcn_readlane((int)v, AMAX_WORDS);
+}
+// 1: the tensor's block maxima span at most 2^GUARD_EXP (am = maximum, nb = word-1 maximum; am is finite and non-zero)
+__device__ __forceinline__ bool amax_narrow(unsigned am, unsigned nb) {
+    if (nb == 0u) return false;                                  // no block reported its minimum: range unknown
+    return __uint_as_float(am) <= __uint_as_float(~nb) * (float)(1 << GUARD_EXP);
+}
 __device__ __forceinline__ Quant quant_select(const unsigned* a_amax, const unsigned* b_amax) {
     Quant q = {0, 1.f, 1.f, 0};
     if (a_amax == nullptr || b_amax == nullptr) return q;
-    const unsigned am = amax_read_wave(a_amax), bm = amax_read_wave(b_amax);
+    unsigned am, an, bm, bn;
+    amax_read_wave2(a_amax, am, an);
+    amax_read_wave2(b_amax, bm, bn);
     if (am >= 0x7f800000u || bm >= 0x7f800000u) return q;        // an infinite element: exact non-finite semantics live in NP = 6
     if (am == 0u || bm == 0u) return q;                          // a slot nobody wrote (or an all-zero operand): magnitude unknown
+    if (!amax_narrow(am, an) || !amax_narrow(bm, bn)) return q;  // a wide-range operand: see GUARD_EXP
     const int ea = scale_bexp(am), eb = scale_bexp(bm);
     q.use3 = 1;
     q.sa = __uint_as_float((unsigned)ea << 23);
@@ -122,6 +150,11 @@ __device__ __forceinline__ float amax_acc(float m, float v) {
 // 8 words of LDS, then ONE agent-scope atomic per block.  Measured r06: device-scope atomics on one 128-byte line retire at
 // ~11 ns each whatever word they hit (MI355X_MICROARCH.md "fanin"), so one per WAVE of an 8192-block element-wise kernel cost
 // 0.23 ms per launch (bn_act_pool_fwd 0.27 -> 1.44 ms per step) -- hence one per block, spread over the slot's sixteen lines.
+// A block with a non-zero maximum also max-accumulates ~bits(its maximum) into word 1 of the same line (the guard of
+// quant_select; an all-zero block -- a masked tile, a dead ReLU region -- says nothing about the tensor's range).  The block
+// maxima are only meaningful if every producer block covers a CONTIGUOUS range of its tensor (tiles, rows, element ranges --
+// not a grid-stride walk).  The trailing barrier lets a kernel commit twice in a row: without it, waves 1.. of the block
+// could overwrite amax_red for the second commit while thread 0 still reads it for the first.
 __device__ __forceinline__ void amax_commit(unsigned* slot, float m) {
     __shared__ unsigned amax_red[16];
     unsigned b = __float_as_uint(m);
@@ -135,8 +168,18 @@ __device__ __forceinline__ void amax_commit(unsigned* slot, float m) {
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < nw; ++w) b = amax_red[w] > b ? amax_red[w] : b;
-        __hip_atomic_fetch_max(slot + (blockIdx.x & (AMAX_WORDS - 1)) * AMAX_STRIDE, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned* line = slot + (blockIdx.x & (AMAX_WORDS - 1)) * AMAX_STRIDE;
+        __hip_atomic_fetch_max(line, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (b != 0u) __hip_atomic_fetch_max(line + 1, ~b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    __syncthreads();
+}
+// contiguous share of an element range for block-uniform walks: [begin, end) of block `blk` out of `nblk`, a multiple of `step`
+__device__ __forceinline__ void block_range(long total, int blk, int nblk, int step, long& begin, long& end) {
+    long per = (total + nblk - 1) / nblk;
+    per = (per + step - 1) / step * step;
+    begin = (long)blk * per;
+    end = begin + per < total ? begin + per : total;
 }
 
 // ---- NP = 6: the six products of a*b = (a1+a2+a3)(b1+b2+b3) that are kept, smallest first.  The five products of weight <= 2^-8

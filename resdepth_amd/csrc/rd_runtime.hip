@@ -14,7 +14,11 @@ namespace rd {
 
 static thread_local char g_err[512] = "";
 
+static void quant_clear();
+// every failing entry point ends here: it also drops the slots rd_quant_next armed for it, which an early return (argument
+// checks, a workspace too small) would otherwise leave for the next call of this thread (include/resdepth_hip.h)
 void set_error(const char* fmt, ...) {
+    quant_clear();
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -64,6 +68,7 @@ int tune(int key) { return g_tune[key].value; }
 
 // ---- magnitude slots of the next call (rd_quant_next) ---------------------------------------------------------------
 static thread_local QuantArgs t_quant = {nullptr, nullptr, nullptr, nullptr, 0};
+static void quant_clear() { t_quant = {nullptr, nullptr, nullptr, nullptr, 0}; }
 QuantArgs quant_take_img() {
     const QuantArgs q = t_quant;
     t_quant = {nullptr, nullptr, nullptr, nullptr, 0};
@@ -254,7 +259,7 @@ static void drain_locked() {
 
 extern "C" {
 
-int rd_version(void) { return 107; }      // 101 (r04): rd_set_splitk_workspace keyed by (device, stream); 102 (r05): rd_host_register; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next, rd_amax, packed operands carry both split forms; 106: rd_plan_*; 107: rd_quant_next_img (per-image magnitude slots)
+int rd_version(void) { return 108; }      // 101 (r04): rd_set_splitk_workspace keyed by (device, stream); 102 (r05): rd_host_register; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next, rd_amax, packed operands carry both split forms; 106: rd_plan_*; 107: rd_quant_next_img (per-image magnitude slots); 108: slot word 1 = complement of the smallest non-zero block maximum (three-product guard), a failing call clears the armed slots
 
 const char* rd_last_error_string(void) { return rd::g_err; }
 

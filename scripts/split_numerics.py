@@ -50,42 +50,97 @@ def flavour(name, shape, g, role):
     raise ValueError(name)
 
 
+# wide-range flavours (split2h: one scale per operand TENSOR): built from randn operands after the fact, see wide()
+WIDE = ("mates20", "mates30", "half30", "chan24")
+CHAN24 = [3, 17, 40, 99, 257]      # the channels chan24 scales by 2^-24
+
+
+def wide(fl, x, wt, gy, w_in_dim):
+    """mates20 / mates30: image 1 of the activation operands is image 0's distribution x 2^-20 / 2^-30; half30: the lower half of
+    the rows of every image x 2^-30.  Returns (x, wt, gy, gyw): gyw is the gradient operand of the WEIGHT gradient, whose
+    contraction runs over pixels -- it is zero wherever the operand is large (what a masked tile gives), so every weight-gradient
+    output comes from the small part alone.  chan24: input channels CHAN24 of x and of the weight (dimension w_in_dim) x 2^-24,
+    inside every producer block (the case a per-tensor guard cannot see); gyw = gy."""
+    x, wt, gy = x.clone(), wt.clone(), gy.clone()
+    gyw = gy.clone()
+    if fl in ("mates20", "mates30"):
+        f = 2.0 ** (-20 if fl == "mates20" else -30)
+        x[1] *= f
+        gy[1] *= f
+        gyw[0] = 0.0
+    elif fl == "half30":
+        x[:, :, x.shape[2] // 2:] *= 2.0 ** -30
+        gy[:, :, gy.shape[2] // 2:] *= 2.0 ** -30
+        gyw[:, :, :gyw.shape[2] // 2] = 0.0
+    elif fl == "chan24":
+        x[:, CHAN24] *= 2.0 ** -24
+        sel = [slice(None)] * wt.dim()
+        sel[w_in_dim] = CHAN24
+        wt[tuple(sel)] *= 2.0 ** -24
+    else:
+        raise ValueError(fl)
+    return x, wt, gy, gyw
+
+
 def nerr(out, ref, den):
     e = (out.double() - ref).abs() / (den + 1e-300)
     return float(e.max()) / U, float(e.pow(2).mean().sqrt()) / U
 
 
-def conv_cases(fl, g, n=2, h=16, w=16, cin=512, cout=128):
-    x = flavour(fl, (n, cin, h, w), g, "a")
-    wt = flavour(fl, (cout, cin, 3, 3), g, "b")
-    gy = flavour("randn" if fl == "tiny" else fl, (n, cout, h, w), g, "a")      # tiny * tiny would underflow to 0
-    xd, wd_, gd = x.double(), wt.double(), gy.double()
-    ref = {"fwd": F.conv2d(xd, wd_, None, 1, 1), "dgrad": F.conv_transpose2d(gd, wd_, None, 1, 1),
-           "wgrad": torch.nn.grad.conv2d_weight(xd, wt.shape, gd, stride=1, padding=1)}
-    den = {"fwd": F.conv2d(xd.abs(), wd_.abs(), None, 1, 1), "dgrad": F.conv_transpose2d(gd.abs(), wd_.abs(), None, 1, 1),
-           "wgrad": torch.nn.grad.conv2d_weight(xd.abs(), wt.shape, gd.abs(), stride=1, padding=1)}
+def floor39(op, a, b):
+    """2^-39 (amax(a) sum_k |b_k| + amax(b) sum_k |a_k|) per output of the bilinear op(a, b), both sums over the output's own K
+    terms: what the split may lose on elements below 2^-18 of their tensor's maximum (the bound for an arbitrary
+    tensor, which the guard does not narrow when small values sit inside every producer block)"""
+    return 2.0 ** -39 * (float(a.abs().max()) * op(torch.ones_like(a), b.abs()) + float(b.abs().max()) * op(a.abs(), torch.ones_like(b)))
+
+
+def conv_cases(fl, g, n=2, h=16, w=16, cin=512, cout=128, floor=False):
+    base = "randn" if fl in WIDE else fl
+    x = flavour(base, (n, cin, h, w), g, "a")
+    wt = flavour(base, (cout, cin, 3, 3), g, "b")
+    gy = flavour("randn" if fl == "tiny" else base, (n, cout, h, w), g, "a")      # tiny * tiny would underflow to 0
+    gyw = gy
+    if fl in WIDE:
+        x, wt, gy, gyw = wide(fl, x, wt, gy, 1)
+    xd, wd_, gd, gwd = x.double(), wt.double(), gy.double(), gyw.double()
+    fwd = lambda a, b: F.conv2d(a, b, None, 1, 1)
+    dgrad = lambda a, b: F.conv_transpose2d(a, b, None, 1, 1)
+    wgrad = lambda a, b: torch.nn.grad.conv2d_weight(b, wt.shape, a, stride=1, padding=1)      # a = gradient, b = x
+    ops_ = {"fwd": (fwd, xd, wd_), "dgrad": (dgrad, gd, wd_), "wgrad": (wgrad, gwd, xd)}
+    ref = {k: op(a, b) for k, (op, a, b) in ops_.items()}
+    den = {k: op(a.abs(), b.abs()) for k, (op, a, b) in ops_.items()}
 
     def run():
         wf, wdd = ops.pack_conv3x3_weight(wt.to(DEV))
         return {"fwd": nchw(ops.conv3x3_fwd(nhwc(x), wf)), "dgrad": nchw(ops.conv3x3_bwd_data(nhwc(gy), wdd)),
-                "wgrad": ops.conv3x3_bwd_weight(nhwc(x), nhwc(gy)).cpu()}
+                "wgrad": ops.conv3x3_bwd_weight(nhwc(x), nhwc(gyw)).cpu()}
+    if floor:
+        return ref, den, run, {k: floor39(op, a, b) for k, (op, a, b) in ops_.items()}
     return ref, den, run
 
 
-def convt_cases(fl, g, n=2, h=16, w=16, c=512):
-    x = flavour(fl, (n, c, h, w), g, "a")
-    wt = flavour(fl, (c, c, 2, 2), g, "b")
-    gy = flavour("randn" if fl == "tiny" else fl, (n, c, 2 * h, 2 * w), g, "a")
-    xd, wd_, gd = x.double(), wt.double(), gy.double()
-    ref = {"fwd": F.conv_transpose2d(xd, wd_, None, 2), "dgrad": F.conv2d(gd, wd_, None, 2),
-           "wgrad": torch.nn.grad.conv2d_weight(gd, wt.shape, xd, stride=2)}
-    den = {"fwd": F.conv_transpose2d(xd.abs(), wd_.abs(), None, 2), "dgrad": F.conv2d(gd.abs(), wd_.abs(), None, 2),
-           "wgrad": torch.nn.grad.conv2d_weight(gd.abs(), wt.shape, xd.abs(), stride=2)}
+def convt_cases(fl, g, n=2, h=16, w=16, c=512, floor=False):
+    base = "randn" if fl in WIDE else fl
+    x = flavour(base, (n, c, h, w), g, "a")
+    wt = flavour(base, (c, c, 2, 2), g, "b")
+    gy = flavour("randn" if fl == "tiny" else base, (n, c, 2 * h, 2 * w), g, "a")
+    gyw = gy
+    if fl in WIDE:
+        x, wt, gy, gyw = wide(fl, x, wt, gy, 0)
+    xd, wd_, gd, gwd = x.double(), wt.double(), gy.double(), gyw.double()
+    fwd = lambda a, b: F.conv_transpose2d(a, b, None, 2)
+    dgrad = lambda a, b: F.conv2d(a, b, None, 2)
+    wgrad = lambda a, b: torch.nn.grad.conv2d_weight(a, wt.shape, b, stride=2)      # a = gradient, b = x
+    ops_ = {"fwd": (fwd, xd, wd_), "dgrad": (dgrad, gd, wd_), "wgrad": (wgrad, gwd, xd)}
+    ref = {k: op(a, b) for k, (op, a, b) in ops_.items()}
+    den = {k: op(a.abs(), b.abs()) for k, (op, a, b) in ops_.items()}
 
     def run():
         wtf, wtd = ops.pack_convt2x2_weight(wt.to(DEV))
         return {"fwd": nchw(ops.convt2x2_fwd(nhwc(x), wtf, None, None)), "dgrad": nchw(ops.convt2x2_bwd_data(nhwc(gy), wtd)),
-                "wgrad": ops.convt2x2_bwd_weight(nhwc(x), nhwc(gy)).cpu()}
+                "wgrad": ops.convt2x2_bwd_weight(nhwc(x), nhwc(gyw)).cpu()}
+    if floor:
+        return ref, den, run, {k: floor39(op, a, b) for k, (op, a, b) in ops_.items()}
     return ref, den, run
 
 
@@ -93,7 +148,7 @@ def main():
     _lib.load()
     print(f"{'op':28s} {'flavour':7s} | split e_max e_rms [u] | f32 e_max e_rms [u]")
     for fam, mk, tiles in (("conv3x3", conv_cases, (-1, 0, 1, 2)), ("convT2x2", convt_cases, (-1,))):
-        for fl in ("randn", "pos", "range", "tiny", "int24"):
+        for fl in ("randn", "pos", "range", "tiny", "int24") + WIDE:
             for tile in tiles:
                 g = torch.Generator().manual_seed(7)
                 ref, den, run = mk(fl, g)

@@ -48,7 +48,10 @@ def _slot_max(t):
 
 
 @pytest.mark.parametrize("family,tile", [("conv", -1), ("conv", 0), ("conv", 1), ("conv", 2), ("convt", -1)])
-@pytest.mark.parametrize("flavour", ["randn", "pos", "range", "int24", "tiny"])
+# mates20 / mates30 / half30 (split_numerics.wide): outputs computed only from operands 2^-20 .. 2^-30 below a large element
+# elsewhere in the same tensor -- on one scale per tensor they would be 2^-9-class (hundreds of u); the slot guard
+# (rd_mfma_dev.h: quant_select) must send them to the six-product body
+@pytest.mark.parametrize("flavour", ["randn", "pos", "range", "int24", "tiny", "mates20", "mates30", "half30"])
 def test_per_op_error_bound_and_below_the_exact_f32_chain(lib, family, tile, flavour):
     import split_numerics as SN
     g = torch.Generator().manual_seed(7)
@@ -68,6 +71,71 @@ def test_per_op_error_bound_and_below_the_exact_f32_chain(lib, family, tile, fla
         assert s_max <= 12.0 + 2.5 * f_max + 4.0, (family, tile, flavour, k, s_max, f_max)
         # measured (r06): 0.17 .. 0.23 u rms on randn (exact-f32: 0.34 .. 0.47), 1.8 .. 5.9 on pos (2.8 .. 16.5), 1.2 .. 1.8 on range
         assert s_rms <= 1.5 * f_rms + 0.5, (family, tile, flavour, k, s_rms, f_rms)
+
+
+@pytest.mark.parametrize("family,tile", [("conv", -1), ("conv", 0), ("conv", 1), ("conv", 2), ("convt", -1)])
+def test_channelwise_small_operands_keep_the_absolute_contract(lib, family, tile):
+    """chan24: a few input channels of x and of the weight x 2^-24 -- inside every producer block, so the guard does not fire and
+    the three-product body runs.  No relative bar: the documented bound for an arbitrary tensor, per output,
+    |out - ref64| <= 12 u sum|a||b| + 2^-39 (amax(a) sum|b| + amax(b) sum|a|) + (the exact-f32 chain's own error).  It fails if the
+    fp16 terms stop keeping subnormals or the scale is derived wrongly."""
+    import split_numerics as SN
+    g = torch.Generator().manual_seed(7)
+    ref, den, run, floor = (SN.conv_cases if family == "conv" else SN.convt_cases)("chan24", g, floor=True)
+    lib.tune_set("nt_tile", tile)
+    out = run()
+    lib.tune_set("mfma_f32", 1)
+    exact = run()
+    lib.tune_set("mfma_f32", 0)
+    lib.tune_set("mfma_products", 6)
+    six = run()
+    lib.tune_set("mfma_products", 3)
+    for k in ref:
+        if tile != -1 and k == "wgrad":
+            continue
+        assert torch.isfinite(out[k]).all()
+        err = (out[k].double() - ref[k]).abs()
+        bound = 16 * U * den[k] + floor[k] + 2.5 * (exact[k].double() - ref[k]).abs()
+        assert bool((err <= bound).all()), (family, tile, k, float((err / bound).max()))
+        assert not torch.equal(out[k], six[k]), (family, tile, k, "the three-product body did not run")
+
+
+@pytest.mark.parametrize("flavour", ["mates30", "half30"])
+def test_conv1x1_wide_range_operands(lib, flavour):
+    """rd_conv1x1_* take slots as well (operands tagged by rd_amax): the same wide-range construction and bar"""
+    from resdepth_amd import ops
+    g = torch.Generator().manual_seed(13)
+    n, h, w, cin, cout = 2, 16, 16, 512, 128
+    x = torch.randn(n, h, w, cin, generator=g)
+    wt = torch.randn(cout, cin, generator=g) * 0.05
+    gy = torch.randn(n, h, w, cout, generator=g)
+    gyw = gy.clone()
+    if flavour == "mates30":
+        x[1] *= 2.0 ** -30
+        gy[1] *= 2.0 ** -30
+        gyw[0] = 0.0
+    else:
+        x[:, h // 2:] *= 2.0 ** -30
+        gy[:, h // 2:] *= 2.0 ** -30
+        gyw[:, :h // 2] = 0.0
+    xd, wd, gd, gwd = x.double(), wt.double(), gy.double(), gyw.double()
+    ref = {"fwd": xd @ wd.t(), "dgrad": gd @ wd, "wgrad": gwd.reshape(-1, cout).t() @ xd.reshape(-1, cin)}
+    den = {"fwd": xd.abs() @ wd.abs().t(), "dgrad": gd.abs() @ wd.abs(), "wgrad": gwd.abs().reshape(-1, cout).t() @ xd.abs().reshape(-1, cin)}
+
+    def run():
+        tg = lambda t: ops.amax_of(t.to(DEV))
+        wf, wtd = ops.pack_conv1x1_weight(wt.view(cout, cin, 1, 1).to(DEV))      # packed operands (both split forms)
+        return {"fwd": ops.conv1x1_fwd(tg(x), wf).cpu(), "dgrad": ops.conv1x1_bwd_data(tg(gy), wtd).cpu(),
+                "wgrad": ops.conv1x1_bwd_weight(tg(x), tg(gyw)).reshape(cout, cin).cpu()}
+    out = run()
+    lib.tune_set("mfma_f32", 1)
+    exact = run()
+    lib.tune_set("mfma_f32", 0)
+    import split_numerics as SN
+    for k in ref:
+        s_max, _ = SN.nerr(out[k], ref[k], den[k])
+        f_max, _ = SN.nerr(exact[k], ref[k], den[k])
+        assert s_max <= 12.0 + 2.5 * f_max + 4.0, (flavour, k, s_max, f_max)
 
 
 def test_three_product_body_runs_when_slots_are_given_and_six_product_body_when_not(lib):
@@ -169,6 +237,61 @@ def test_every_producer_leaves_the_exact_maximum_in_its_slot(lib):
         if ops.conv3x3_first_fwd_act_available(x0, c):
             a0, p0 = ops.conv3x3_first_fwd_act(x0, w0, mean, invstd, gamma, beta, 0.0, None, pool=True)
             assert _slot_max(p0) == float(p0.abs().max())
+
+
+@pytest.mark.parametrize("c,n,h,w", [(64, 2, 32, 32), (64, 3, 16, 48), (128, 2, 16, 32), (128, 1, 32, 64)])
+def test_fwd_act_commits_both_slots_exactly_when_the_pool_drops_the_maximum(lib, c, n, h, w):
+    """rd_conv3x3_fwd_act with pool=True commits twice in a row (out slot, pooled slot): the 64- and 128-channel patch kernels at
+    a LeakyReLU slope > 0 on data whose largest |a| is a negative value that the max-pool drops.  Each slot must hold exactly its
+    tensor's maximum (amax_commit's trailing barrier: the second commit must not overwrite the first one's LDS words)."""
+    from resdepth_amd import ops
+    g = torch.Generator().manual_seed(c + h)
+    x = ops.amax_of(torch.randn(n, h, w, 64, generator=g).to(DEV))
+    w3 = (torch.randn(c, 64, 3, 3, generator=g) * 0.05).to(DEV)
+    shift = torch.randn(c, generator=g).to(DEV) * 0.1
+    shift[c // 3] = -60.0                 # one channel far below zero: its most negative a is the largest |a|, never pooled
+    wff = ops.pack_conv3x3_weight_folded(w3, (torch.rand(c, generator=g) + 0.5).to(DEV))
+    with lib.AmaxPool(DEV):
+        aa, pp = ops.conv3x3_fwd_act(x, wff, shift, 0.5, pool=True)
+    amax_a, amax_p = float(aa.abs().max()), float(pp.abs().max())
+    assert amax_a > amax_p and float(aa.min()) == -amax_a, "the construction must put the largest |a| where the pool drops it"
+    assert _slot_max(aa) == amax_a and _slot_max(pp) == amax_p
+
+
+def test_a_rejected_call_leaves_no_slots_armed(lib):
+    """rd_quant_next arms slots for the NEXT call; a call that fails its argument checks (here: a workspace too small) must clear
+    them, or the next ordinary call of this thread would take them (include/resdepth_hip.h)."""
+    import threading
+    from resdepth_amd import ops
+    L = lib.load()
+    g = torch.Generator().manual_seed(17)
+    n, h, w, c = 2, 16, 16, 64
+    z = (torch.randn(n, h, w, c, generator=g) * 3).to(DEV)
+    mean, invstd = torch.randn(c, generator=g).to(DEV) * 0.1, (torch.rand(c, generator=g) + 0.5).to(DEV)
+    gamma, beta = (torch.rand(c, generator=g) + 0.5).to(DEV), torch.randn(c, generator=g).to(DEV) * 0.1
+    x = torch.randn(n, h, w, c, generator=g).to(DEV)
+    wf, _ = ops.pack_conv3x3_weight((torch.randn(c, c, 3, 3, generator=g) * 0.05).to(DEV))
+    zz = torch.empty(n, h, w, c, device=DEV)
+    sums = torch.empty(2 * c, dtype=torch.float64, device=DEV)
+    armed = [torch.zeros(lib.AMAX_WORDS, dtype=torch.int32, device=DEV) for _ in range(4)]
+
+    def ordinary():
+        a, p, _ = ops.bn_act_pool_fwd(z, mean, invstd, gamma, beta, 0.01, True)      # a producer, no pool: no rd_quant_next
+        return a, p, ops.conv3x3_fwd(x, wf)                                          # a consumer without slots
+    L.rd_quant_next(*[t.data_ptr() for t in armed])
+    rc = L.rd_conv3x3_fwd_stats(x.data_ptr(), wf.data_ptr(), zz.data_ptr(), sums.data_ptr(), n, h, w, c, c, None, 0,
+                                torch.cuda.current_stream().cuda_stream)
+    assert rc != 0 and b"workspace" in L.rd_last_error_string()
+    got = ordinary()
+    torch.cuda.synchronize()
+    fresh = []
+    t = threading.Thread(target=lambda: fresh.append(ordinary()))
+    t.start()
+    t.join()
+    torch.cuda.synchronize()
+    assert all(int(s.abs().max()) == 0 for s in armed), "a slot armed before the rejected call was taken by a later one"
+    for a, b in zip(got, fresh[0]):
+        assert torch.equal(a, b)
 
 
 def test_results_are_bit_reproducible_and_weight_gradients_match_fp64(lib):

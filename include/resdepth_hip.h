@@ -40,7 +40,7 @@ typedef void* rd_stream_t; /* hipStream_t */
 #define RD_ERR_WS 2
 #define RD_ERR_HIP 3
 
-int rd_version(void); /* 100: r01-r03; 101: rd_set_splitk_workspace registrations belong to (current device, stream); 102: rd_host_register & co; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next / rd_amax, packed operands hold both split forms; 106: rd_plan_*; 107: rd_quant_next_img */
+int rd_version(void); /* 100: r01-r03; 101: rd_set_splitk_workspace registrations belong to (current device, stream); 102: rd_host_register & co; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next / rd_amax, packed operands hold both split forms; 106: rd_plan_*; 107: rd_quant_next_img; 109: rd_assemble_grid_tiles */
 /* Arithmetic of the split MFMA kernels -- ONE library, chosen per launch (csrc/rd_mfma_dev.h):
  *   6  "split3"   x = x1 + x2 + x3 (three bf16 terms, exact), six products per multiply on v_mfma_f32_32x32x16_bf16.  No
  *                 assumption about the operands; what every launch falls back to.
@@ -473,6 +473,27 @@ int rd_assemble_patches(const float* dsm_in, const float* dsm_gt, const float* o
                         const int* pair_idx, int views, const int* pos, const int* aug, const float* dsm_mean,
                         float dsm_std, const float* ortho_mean, float ortho_std, float nodata, int n, int tile, int width,
                         float* input, float* target, uint8_t* mask, rd_stream_t s);
+
+/* ---- validation / inference grid tiles from rasters resident in HBM (lib/DsmOrthoDataset.py:161-291 for sampling_strategy
+ * 'val' / 'test', _get_dsm_loss_mask :434-470; replaces the per-tile numpy slicing, np.ma.mean, torchvision Normalize and
+ * DataLoader collation of test.py:170-189 and train.py:155-161).  samples[i * RD_GRID_SAMPLE_INTS ..] = (uly, ulx, box uly,
+ * box ulx, box lry, box lrx, pair, unused): the tile's upper-left raster pixel, its non-overlap box in tile coordinates
+ * (inclusive) and a row of pair_planes [n_pairs][views] (plane indices into the planar ortho stack of n_planes planes of
+ * height x width).  input[i] = cat(DSM channel if dsm_channel, the `views` ortho planes of the pair); target[i] = DSM target;
+ * mask[i] = inside the box & gt != 0 & gt != nodata (dsm_gt / target / mask nullable together).  Normalisation
+ * (x - mean) / std rounded as torch's sub_ / div_: *_mode 0 = raw values (mean 0), 1 = the given mean, 2 = the tile's mean
+ * (DSM: over input pixels != nodata; orthos: over all views * tile^2 values), fp64 sums rounded once to fp32, fixed order
+ * (a tile's mean depends on its pixels alone; an all-nodata tile gets 0/0 = NaN, as rd_patch_sums' callers do).
+ * dsm_mean_out[i] = the DSM mean used (0 for mode 0).  A sample outside the raster or with a bad pair / plane index yields
+ * NaN input / target / dsm_mean and an empty mask (nothing is read).  tile: a multiple of 8.  Workspace (only for mode 2):
+ * rd_assemble_grid_tiles_ws_bytes(n, tile).  Kernels: grid_tile_sums (mode 2 only), grid_tile_write. */
+#define RD_GRID_SAMPLE_INTS 8
+size_t rd_assemble_grid_tiles_ws_bytes(int n, int tile);
+int rd_assemble_grid_tiles(const float* dsm_in, const float* dsm_gt, const float* ortho_planes, int n_planes, int height,
+                           int width, const int* samples, const int* pair_planes, int n_pairs, int views, int dsm_channel,
+                           int n, int tile, float nodata, int dsm_mode, float dsm_mean, float dsm_std, int ortho_mode,
+                           float ortho_mean, float ortho_std, float* input, float* target, uint8_t* mask, float* dsm_mean_out,
+                           void* ws, size_t ws_bytes, rd_stream_t s);
 
 /* ---- masked residual statistics of a refined DSM (lib/evaluation.py:11-131) ------------------------ */
 /* residual r = raster - gt where raster != nodata, gt != nodata, mask (nullable) != 0 and, if threshold > 0,

@@ -137,6 +137,8 @@ SIGNATURES = {
     "rd_copy_to_host_async": (I, [P, P, SZ, P]),
     "rd_patch_sums": (I, [P, LL, P, I, P, I, I, I, F, I, P, P]),
     "rd_assemble_patches": (I, [P, P, P, LL, P, I, P, P, P, F, P, F, F, I, I, I, P, P, P, P]),
+    "rd_assemble_grid_tiles_ws_bytes": (SZ, [I, I]),
+    "rd_assemble_grid_tiles": (I, [P, P, P, I, I, I, P, P, I, I, I, I, I, F, I, F, F, I, F, F, P, P, P, P, P, SZ, P]),
     "rd_residual_stats_ws_bytes": (SZ, [LL]),
     "rd_residual_stats": (I, [P, P, P, LL, D, D, P, P, SZ, P]),
     "rd_dilate_mask": (I, [P, P, I, I, I, P]),

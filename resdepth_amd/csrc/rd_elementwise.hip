@@ -1230,6 +1230,160 @@ __global__ __launch_bounds__(256) void assemble_patches_kernel(
     }
 }
 
+// ---- validation / inference grid tiles (lib/DsmOrthoDataset.py:161-291, sampling_strategy 'val' / 'test') ------------
+// Sample row (RD_GRID_SAMPLE_INTS ints): uly, ulx, box uly, box ulx, box lry, box lrx (tile coordinates, inclusive), image-pair
+// index, unused.  Two kernels: grid_tile_sums writes fp64 partial sums per (tile, slab of GRID_SLAB_ROWS rows) with a fixed
+// in-block tree; grid_tile_write adds the slab partials of its tile in slab order, so a tile's mean depends on the tile's
+// pixels and T alone (not on the batch, the tile's place in it or the launch shape).  A lane owns four adjacent pixels:
+// 16-B loads when the source rows are 16-B aligned (ulx, W and the plane stride multiples of 4), else four 4-B loads;
+// 16-B stores, 4-B mask stores.
+constexpr int GRID_SLAB_ROWS = 8;
+
+struct GridSample {
+    int uly, ulx, b_uly, b_ulx, b_lry, b_lrx, pair;
+    bool ok, vec;
+};
+
+__device__ __forceinline__ GridSample grid_sample(const int* __restrict__ samples, int i, const int* __restrict__ pair_planes,
+                                                  int n_pairs, int V, int n_planes, int H, int W, long plane_stride, int T,
+                                                  int aligned) {
+    const int* s = samples + (long)i * RD_GRID_SAMPLE_INTS;
+    GridSample g;
+    g.uly = s[0]; g.ulx = s[1]; g.b_uly = s[2]; g.b_ulx = s[3]; g.b_lry = s[4]; g.b_lrx = s[5]; g.pair = s[6];
+    g.ok = g.uly >= 0 && g.ulx >= 0 && g.uly + T <= H && g.ulx + T <= W;
+    if (V > 0) {
+        g.ok = g.ok && g.pair >= 0 && g.pair < n_pairs;
+        for (int j = 0; g.ok && j < V; ++j) {
+            const int p = pair_planes[g.pair * V + j];
+            g.ok = p >= 0 && p < n_planes;
+        }
+    }
+    g.vec = aligned && ((g.ulx | W | (int)(plane_stride & 3)) & 3) == 0;
+    return g;
+}
+
+__device__ __forceinline__ float4 ld4(const float* __restrict__ p, bool vec) {
+    if (vec) return *reinterpret_cast<const float4*>(p);
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+__global__ __launch_bounds__(256) void grid_tile_sums(const float* __restrict__ dsm_in, const float* __restrict__ ortho,
+                                                      long plane_stride, int H, int W, int n_planes,
+                                                      const int* __restrict__ samples, const int* __restrict__ pair_planes,
+                                                      int n_pairs, int V, int T, float nodata, int want_dsm, int want_ortho,
+                                                      int aligned, double* __restrict__ ws) {
+    __shared__ double red[3][256];
+    const int i = blockIdx.x, slab = blockIdx.y, S = gridDim.y, t = threadIdx.x;
+    const GridSample g = grid_sample(samples, i, pair_planes, n_pairs, V, n_planes, H, W, plane_stride, T, aligned);
+    double sd = 0.0, cd = 0.0, so = 0.0;
+    if (g.ok) {
+        const int TQ = T / 4;
+        for (int e = t; e < GRID_SLAB_ROWS * TQ; e += 256) {
+            const int r = slab * GRID_SLAB_ROWS + e / TQ, c = (e % TQ) * 4;
+            const long off = (long)(g.uly + r) * W + g.ulx + c;
+            if (want_dsm) {
+                const float4 v = ld4(dsm_in + off, g.vec);
+                if (v.x != nodata) { sd += v.x; cd += 1.0; }
+                if (v.y != nodata) { sd += v.y; cd += 1.0; }
+                if (v.z != nodata) { sd += v.z; cd += 1.0; }
+                if (v.w != nodata) { sd += v.w; cd += 1.0; }
+            }
+            if (want_ortho) {
+                for (int j = 0; j < V; ++j) {
+                    const float4 v = ld4(ortho + (long)pair_planes[g.pair * V + j] * plane_stride + off, g.vec);
+                    so += v.x; so += v.y; so += v.z; so += v.w;
+                }
+            }
+        }
+    }
+    red[0][t] = sd;
+    red[1][t] = cd;
+    red[2][t] = so;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) {
+            red[0][t] += red[0][t + off];
+            red[1][t] += red[1][t + off];
+            red[2][t] += red[2][t + off];
+        }
+        __syncthreads();
+    }
+    if (t < 3) ws[((long)i * S + slab) * 4 + t] = red[t][0];
+}
+
+__global__ __launch_bounds__(256) void grid_tile_write(
+    const float* __restrict__ dsm_in, const float* __restrict__ dsm_gt, const float* __restrict__ ortho, long plane_stride,
+    int H, int W, int n_planes, const int* __restrict__ samples, const int* __restrict__ pair_planes, int n_pairs, int V,
+    int dsm_channel, int T, int S, float nodata, int dsm_mode, float dsm_mean_fixed, float dsm_std, int ortho_mode,
+    float ortho_mean_fixed, float ortho_std, int aligned, const double* __restrict__ ws, int rows_per_block, float* __restrict__ input,
+    float* __restrict__ target, uint8_t* __restrict__ mask, float* __restrict__ dsm_mean_out) {
+    const int i = blockIdx.x, p = blockIdx.y, rb = blockIdx.z, t = threadIdx.x;
+    const int C = dsm_channel + V;
+    const GridSample g = grid_sample(samples, i, pair_planes, n_pairs, V, n_planes, H, W, plane_stride, T, aligned);
+    // the tile's means: slab partials in slab order, then one rounding to fp32 (GpuPatchSampler's (sum / count).float())
+    float dmean = dsm_mode == 1 ? dsm_mean_fixed : 0.f;
+    float omean = ortho_mode == 1 ? ortho_mean_fixed : 0.f;
+    if (dsm_mode == 2) {
+        double s = 0.0, c = 0.0;
+        for (int k = 0; k < S; ++k) {
+            s += ws[((long)i * S + k) * 4];
+            c += ws[((long)i * S + k) * 4 + 1];
+        }
+        dmean = (float)(s / c);
+    }
+    if (ortho_mode == 2 && V > 0 && p >= dsm_channel && p < C) {
+        double s = 0.0;
+        for (int k = 0; k < S; ++k) s += ws[((long)i * S + k) * 4 + 2];
+        omean = (float)(s / ((double)V * T * T));
+    }
+    if (p == 0 && rb == 0 && t == 0) dsm_mean_out[i] = g.ok ? dmean : __int_as_float(0x7fc00000);
+    const float* src;
+    float* dst;
+    float mean = dmean, sdv = dsm_std;
+    int mode = dsm_mode;
+    if (p < dsm_channel) {
+        src = dsm_in;
+        dst = input + ((long)i * C + p) * T * T;
+    } else if (p < C) {
+        src = g.ok ? ortho + (long)pair_planes[g.pair * V + p - dsm_channel] * plane_stride : ortho;
+        dst = input + ((long)i * C + p) * T * T;
+        mean = omean;
+        sdv = ortho_std;
+        mode = ortho_mode;
+    } else {
+        src = dsm_gt;
+        dst = target + (long)i * T * T;
+    }
+    const bool is_target = p == C;
+    const int TQ = T / 4, r0 = rb * rows_per_block, r1 = min(T, r0 + rows_per_block);
+    const float qnan = __int_as_float(0x7fc00000);
+    for (int e = t; e < (r1 - r0) * TQ; e += 256) {
+        const int r = r0 + e / TQ, c = (e % TQ) * 4;
+        float4 v = make_float4(qnan, qnan, qnan, qnan), o = v;
+        if (g.ok) {
+            v = ld4(src + (long)(g.uly + r) * W + g.ulx + c, g.vec);
+            o = v;
+            if (mode) {
+                o.x = __fdiv_rn(__fsub_rn(v.x, mean), sdv);
+                o.y = __fdiv_rn(__fsub_rn(v.y, mean), sdv);
+                o.z = __fdiv_rn(__fsub_rn(v.z, mean), sdv);
+                o.w = __fdiv_rn(__fsub_rn(v.w, mean), sdv);
+            }
+        }
+        *reinterpret_cast<float4*>(dst + (long)r * T + c) = o;
+        if (is_target) {
+            // lib/DsmOrthoDataset.py:434-470: inside the non-overlap box, gt != 0 and gt != nodata
+            const bool row_in = g.ok && r >= g.b_uly && r <= g.b_lry;
+            uchar4 m;
+            m.x = row_in && c >= g.b_ulx && c <= g.b_lrx && v.x != 0.f && v.x != nodata;
+            m.y = row_in && c + 1 >= g.b_ulx && c + 1 <= g.b_lrx && v.y != 0.f && v.y != nodata;
+            m.z = row_in && c + 2 >= g.b_ulx && c + 2 <= g.b_lrx && v.z != 0.f && v.z != nodata;
+            m.w = row_in && c + 3 >= g.b_ulx && c + 3 <= g.b_lrx && v.w != 0.f && v.w != nodata;
+            *reinterpret_cast<uchar4*>(mask + (long)i * T * T + (long)r * T + c) = m;
+        }
+    }
+}
+
 // ---- layout ---------------------------------------------------------------------------------------
 __global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int C, int HW) {
     const long total = (long)N * C * HW;
@@ -1982,6 +2136,54 @@ int rd_assemble_patches(const float* dsm_in, const float* dsm_gt, const float* o
                        dsm_in, dsm_gt, ortho_planes, (long)plane_stride, pair_idx, views, pos, aug, dsm_mean, dsm_std,
                        ortho_mean, ortho_std, nodata, n, tile, width, input, target, mask);
     RD_LAUNCH_CHECK("assemble_patches");
+    return RD_OK;
+}
+
+size_t rd_assemble_grid_tiles_ws_bytes(int n, int tile) {
+    if (n <= 0 || tile <= 0) return 0;
+    return (size_t)n * (size_t)((tile + GRID_SLAB_ROWS - 1) / GRID_SLAB_ROWS) * 4 * sizeof(double);
+}
+
+int rd_assemble_grid_tiles(const float* dsm_in, const float* dsm_gt, const float* ortho_planes, int n_planes, int height,
+                           int width, const int* samples, const int* pair_planes, int n_pairs, int views, int dsm_channel,
+                           int n, int tile, float nodata, int dsm_mode, float dsm_mean, float dsm_std, int ortho_mode,
+                           float ortho_mean, float ortho_std, float* input, float* target, uint8_t* mask, float* dsm_mean_out,
+                           void* ws, size_t ws_bytes, rd_stream_t s) {
+    RD_REQUIRE(dsm_in && samples && input && dsm_mean_out && n > 0 && height >= tile && width >= tile && views >= 0,
+               "rd_assemble_grid_tiles: bad arguments");
+    RD_REQUIRE(tile >= GRID_SLAB_ROWS && tile % GRID_SLAB_ROWS == 0,
+               "rd_assemble_grid_tiles: tile must be a positive multiple of %d (got %d)", GRID_SLAB_ROWS, tile);
+    RD_REQUIRE((dsm_channel == 0 || dsm_channel == 1) && dsm_channel + views >= 1, "rd_assemble_grid_tiles: no input channel");
+    RD_REQUIRE(views == 0 || (ortho_planes && pair_planes && n_pairs > 0 && n_planes > 0),
+               "rd_assemble_grid_tiles: ortho inputs missing");
+    RD_REQUIRE(!dsm_gt || (target && mask), "rd_assemble_grid_tiles: target / mask outputs missing");
+    RD_REQUIRE(dsm_mode >= 0 && dsm_mode <= 2 && ortho_mode >= 0 && ortho_mode <= 2, "rd_assemble_grid_tiles: bad mode");
+    const long long plane = (long long)height * width;
+    const int S = tile / GRID_SLAB_ROWS;
+    const int want_dsm = dsm_mode == 2, want_ortho = ortho_mode == 2 && views > 0;
+    if (want_dsm || want_ortho)
+        RD_REQUIRE(ws && ws_bytes >= rd_assemble_grid_tiles_ws_bytes(n, tile),
+                   "rd_assemble_grid_tiles: workspace too small (%zu < %zu bytes)", ws_bytes,
+                   rd_assemble_grid_tiles_ws_bytes(n, tile));
+    RD_REQUIRE(((uintptr_t)input | (uintptr_t)target) % 16 == 0 && (uintptr_t)mask % 4 == 0,
+               "rd_assemble_grid_tiles: input / target must be 16-byte aligned, mask 4-byte aligned");
+    // 16-B loads need 16-B aligned rasters (a caller's view may start anywhere): else every tile takes the 4-B loads
+    const int aligned = (((uintptr_t)dsm_in | (uintptr_t)dsm_gt | (uintptr_t)ortho_planes) % 16) == 0;
+    const int planes_out = dsm_channel + views + (dsm_gt ? 1 : 0);
+    const double px = (double)n * tile * tile;
+    if (want_dsm || want_ortho) {
+        ProfScope ps((hipStream_t)s, "grid_tile_sums", 0, 4.0 * px * (want_dsm + (want_ortho ? views : 0)));
+        RD_LAUNCH(grid_tile_sums, dim3(n, S), dim3(256), 0, (hipStream_t)s, dsm_in, ortho_planes, (long)plane, height, width,
+                  n_planes, samples, pair_planes, n_pairs, views, tile, nodata, want_dsm, want_ortho, aligned, (double*)ws);
+        RD_LAUNCH_CHECK("grid_tile_sums");
+    }
+    const int rows_per_block = 4096 / tile < 1 ? 1 : (4096 / tile > tile ? tile : 4096 / tile);
+    ProfScope ps((hipStream_t)s, "grid_tile_write", 0, px * (8.0 * planes_out + (dsm_gt ? 1.0 : 0.0)));
+    RD_LAUNCH(grid_tile_write, dim3(n, planes_out, cdiv(tile, rows_per_block)), dim3(256), 0, (hipStream_t)s, dsm_in, dsm_gt,
+              ortho_planes, (long)plane, height, width, n_planes, samples, pair_planes, n_pairs, views, dsm_channel, tile, S,
+              nodata, dsm_mode, dsm_mean, dsm_std, ortho_mode, ortho_mean, ortho_std, aligned, (const double*)ws, rows_per_block,
+              input, target, mask, dsm_mean_out);
+    RD_LAUNCH_CHECK("grid_tile_write");
     return RD_OK;
 }
 

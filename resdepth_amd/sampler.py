@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import torch
 
+from . import tiling
 from ._lib import check, load, ptr, stream_ptr
 
 
@@ -148,3 +149,168 @@ class SamplerLoader:
     def __iter__(self):
         return self.sampler.stream_batches(self.n_batches, self.batch_size, self.pairs, generator=self.generator,
                                            augment=self.augment, prefetch=self.prefetch)
+
+
+_VIEW_CHANNELS = ("geom-mono", "geom-stereo", "geom-multiview", "stereo")
+
+
+class GridTileSet:
+    """`loader.dataset` of a GpuGridTiles: what predict_linear_blend and the Trainer read from a dataset (tile_size, stride,
+    raster_shape, len(), `pos` in loader order, `shard` / `shard_plan`), plus the per-sample boxes and pair indices."""
+
+    def __init__(self, tile_size, stride, raster_shape, pos, reg, pair_idx, shard, shard_plan):
+        self.tile_size, self.stride, self.raster_shape = int(tile_size), int(stride), tuple(raster_shape)
+        self.pos, self.reg, self.pair_idx = pos, reg, pair_idx
+        self.shard, self.shard_plan = shard, shard_plan
+
+    def __len__(self):
+        return len(self.pos)
+
+
+class GpuGridTiles:
+    """Validation / inference tiles (sampling_strategy 'val' / 'test' of the reference's DsmOrthoDataset, lib/DsmOrthoDataset.py:
+    161-291 and 373-431) assembled on the GPU from the rasters a GpuPatchSampler keeps in HBM: the regular grid of
+    `area_defn` (lib/rasterutils.py:100-191), per-tile DSM centring, ortho normalisation, target and the loss mask cut to each
+    tile's non-overlap box, collated into device-resident batch dicts in the order and batching of
+    DataLoader(dataset, batch_size, shuffle=False).  Takes the place of `utils.get_dataloader([dataset], sampling_strategy=
+    'test' | 'val', ...)` for predict_linear_blend (test.py:170-189) and the Trainer's valloader (train.py:155-161); both take
+    its batches as they are.  Batch k + 1 is assembled on a side stream while batch k is consumed (`prefetch`, as
+    GpuPatchSampler.stream_batches).
+
+    dsm_mean: None (or 0.0, the reference's `if not self.dsm_mean`) = each tile's mean over its input pixels != nodata; a
+    tile whose input is all nodata gets NaN (0 / 0, as GpuPatchSampler).  The ortho mean / std and the DSM std are the
+    sampler's.  shard=(rank, world): this rank's row band of a 'test' sweep (tiling.band_shards, as SyntheticRasterTiles)."""
+
+    def __init__(self, sampler: GpuPatchSampler, strategy: str, area_defn, input_channels: str = "geom-stereo",
+                 image_pairs=None, stride=None, dsm_mean=None, transform_dsm: bool = True, transform_orthos: bool = True,
+                 batch_size: int = 32, shard=(0, 1), prefetch: int = 1, augment: bool = False,
+                 permute_images_within_pair: bool = False):
+        if augment:
+            raise ValueError("GpuGridTiles: augment=True is not supported (the reference augments 'train' samples only)")
+        if permute_images_within_pair:
+            raise ValueError("GpuGridTiles: permute_images_within_pair=True is not supported")
+        if not isinstance(sampler, GpuPatchSampler):
+            raise ValueError("GpuGridTiles takes one GpuPatchSampler (multi-dataset ConcatDatasets are not supported)")
+        if input_channels not in ("geom",) + _VIEW_CHANNELS:
+            raise ValueError(f"GpuGridTiles: unknown input_channels {input_channels!r}")
+        rank, world = int(shard[0]), int(shard[1])
+        if not 0 <= rank < world:
+            raise ValueError(f"GpuGridTiles: bad shard {shard!r}")
+        if strategy == "val" and world > 1:
+            raise ValueError("GpuGridTiles: a sharded validation set is not supported")
+        if strategy not in ("val", "test"):
+            raise ValueError(f"GpuGridTiles: strategy must be 'val' or 'test' (got {strategy!r}); 'train' is SamplerLoader")
+        if strategy == "val" and sampler.dsm_gt is None:
+            raise ValueError("GpuGridTiles: strategy='val' needs the sampler's ground-truth raster")
+        self.source = sampler                 # not `.sampler`: predict_linear_blend reads that name as a torch sampler
+        t = sampler.tile
+        if t % 8:
+            raise ValueError(f"GpuGridTiles: tile_size must be a multiple of 8 (got {t})")
+        views = input_channels in _VIEW_CHANNELS
+        pairs = None
+        if views:
+            if sampler.orthos is None or not image_pairs:
+                raise ValueError(f"GpuGridTiles: input_channels={input_channels!r} needs the sampler's orthos and image_pairs")
+            pairs = [[int(p) for p in pr] for pr in image_pairs]
+            if len({len(p) for p in pairs}) != 1 or not pairs[0]:
+                raise ValueError("GpuGridTiles: every image pair must have the same number of views")
+            n_planes = sampler.orthos.shape[0]
+            if any(p < 0 or p >= n_planes for pr in pairs for p in pr):
+                raise ValueError(f"GpuGridTiles: an image index is outside the {n_planes} ortho planes")
+        self.strategy, self.input_channels = strategy, input_channels
+        self.views = len(pairs[0]) if views else 0
+        self.dsm_channel = 0 if input_channels == "stereo" else 1
+        self.batch_size, self.prefetch = int(batch_size), int(prefetch)
+        xe, ye = area_defn["x_extent"], area_defn["y_extent"]
+        if len(xe) != len(ye):
+            raise ValueError("GpuGridTiles: area_defn x_extent / y_extent differ in length")
+        for (x0, x1), (y0, y1) in zip(xe, ye):
+            if x0 < 0 or y0 < 0 or x1 >= sampler.w or y1 >= sampler.h or x1 - x0 + 1 < t or y1 - y0 + 1 < t:
+                raise ValueError(f"GpuGridTiles: area x {x0}..{x1}, y {y0}..{y1} does not hold a {t} x {t} tile inside the "
+                                 f"{sampler.h} x {sampler.w} raster")
+        stride, pos, reg, pair_idx = tiling.grid_samples(xe, ye, t, strategy, stride, len(pairs) if views else 1, views)
+        if not 0 < stride <= t:
+            raise ValueError(f"GpuGridTiles: stride must be in 1..{t} (got {stride})")
+        pos, reg, pair_idx, plan = tiling.grid_shard(strategy, pos, reg, pair_idx, t, sampler.h, (rank, world))
+        self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan)
+        # transform modes of rd_assemble_grid_tiles: 0 raw, 1 the given mean, 2 the tile's mean (`not mean`: the reference's test)
+        self.dsm_mode = 0 if not transform_dsm else (2 if not dsm_mean else 1)
+        self.dsm_mean = float(dsm_mean) if self.dsm_mode == 1 else 0.0
+        om = sampler.ortho_mean
+        self.ortho_mode = 0 if not transform_orthos else (2 if not om else 1)
+        self.ortho_mean = float(om) if self.ortho_mode == 1 else 0.0
+        dev = sampler.device
+        n = len(pos)
+        tab = torch.zeros(max(n, 1), 8, dtype=torch.int32)
+        if n:
+            tab[:n, 0:2] = torch.tensor(pos, dtype=torch.int32)
+            tab[:n, 2:6] = torch.tensor(reg, dtype=torch.int32)
+            tab[:n, 6] = torch.tensor(pair_idx, dtype=torch.int32)
+        # uploaded once per loader: the kernels' sample table, the pair -> plane table and the int64 metadata columns
+        self._table = tab.to(dev)
+        self._pair_planes = torch.tensor(pairs, dtype=torch.int32).to(dev) if views else None
+        self._meta = {k: tab[:n, c].to(torch.int64).to(dev) for c, k in enumerate(
+            ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
+             "patch_valid_pixels_lrx"))}
+        self.drop_last = False
+
+    def __len__(self):
+        return -(-len(self.dataset) // self.batch_size)
+
+    def assemble(self, k0: int, k1: int, ws=None):
+        """Samples [k0, k1) of this loader as one batch dict (device tensors), on the current stream."""
+        with torch.cuda.device(self.source.device):      # raw launches go to the current device's stream
+            return self._assemble(int(k0), int(k1), ws)
+
+    def _assemble(self, k0, k1, ws):
+        src, t, dev = self.source, self.source.tile, self.source.device
+        if not 0 <= k0 < k1 <= len(self.dataset):
+            raise ValueError(f"GpuGridTiles: sample range [{k0}, {k1}) outside 0..{len(self.dataset)}")
+        n, v = k1 - k0, self.views
+        c = self.dsm_channel + v
+        inp = torch.empty(n, c, t, t, dtype=torch.float32, device=dev)
+        mean = torch.empty(n, dtype=torch.float32, device=dev)
+        tgt = msk = None
+        if src.dsm_gt is not None:
+            tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
+            msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
+        lib = load()
+        need = lib.rd_assemble_grid_tiles_ws_bytes(n, t)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib.rd_assemble_grid_tiles(
+            ptr(src.dsm_in), ptr(src.dsm_gt), ptr(src.orthos) if v else None, src.orthos.shape[0] if v else 0, src.h, src.w,
+            self._table.data_ptr() + k0 * 8 * 4, ptr(self._pair_planes) if v else None,
+            self._pair_planes.shape[0] if v else 0, v, self.dsm_channel, n, t, src.nodata, self.dsm_mode, self.dsm_mean,
+            src.dsm_std, self.ortho_mode, self.ortho_mean, src.ortho_std, ptr(inp), ptr(tgt), ptr(msk), ptr(mean), ptr(ws),
+            ws.numel(), stream_ptr()), "assemble_grid_tiles")
+        batch = {"input": inp, "dsm_mean": mean, "dsm_std": torch.full((n,), src.dsm_std, device=dev),
+                 "nodata": torch.full((n,), src.nodata, device=dev)}
+        for key, col in self._meta.items():
+            batch[key] = col[k0:k1]
+        if tgt is not None:
+            batch["target"], batch["loss_mask"] = tgt, msk.view(torch.bool)
+        return batch
+
+    def __iter__(self):
+        src = self.source
+        with torch.cuda.device(src.device):
+            side = torch.cuda.Stream(device=src.device)
+            with torch.cuda.stream(side):
+                ws = torch.empty(load().rd_assemble_grid_tiles_ws_bytes(self.batch_size, src.tile), dtype=torch.uint8,
+                                 device=src.device)
+        queue = []
+
+        def produce(k0, k1):
+            with torch.cuda.device(src.device), torch.cuda.stream(side):
+                b = self._assemble(k0, k1, ws)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return b, ev
+
+        for k0, k1 in tiling.batch_bounds(len(self.dataset), self.batch_size):
+            queue.append(produce(k0, k1))
+            if len(queue) > max(0, self.prefetch):
+                yield src._hand_over(queue.pop(0))
+        while queue:
+            yield src._hand_over(queue.pop(0))

@@ -83,3 +83,41 @@ def band_shards(pos: Sequence[Tuple[int, int]], tile_size: int, rows: int, world
         e["hi"] = max(e["c1"], e["y1"]) if e["y1"] is not None else e["c1"]
         e["monotonic"] = mono
     return out
+
+
+def grid_samples(x_extent: Sequence[Tuple[int, int]], y_extent: Sequence[Tuple[int, int]], tile_size: int, strategy: str,
+                 stride: int | None = None, n_pairs: int = 1, views: bool = True):
+    """Sample order of the reference's `_determine_patches` for sampling_strategy 'val' / 'test' (lib/DsmOrthoDataset.py:373-431)
+    -> (stride, positions [(uly, ulx)], boxes [(b_uly, b_ulx, b_lry, b_lrx)], pair indices), one entry per sample.
+    stride None: T/2 for 'test', T for 'val' (:99-104).  'val' with image views (`views`, every input_channels but 'geom')
+    evaluates every pair at every position, pair-major: sample k = (position k % P, pair k // P) for P grid positions.
+    'val' without views and 'test' take the positions once, with pair 0."""
+    if strategy not in ("val", "test"):
+        raise ValueError(f"strategy must be 'val' or 'test' (got {strategy!r})")
+    if stride is None:
+        stride = int(tile_size * 0.5) if strategy == "test" else int(tile_size)
+    pos, reg = regular_grid(x_extent, y_extent, tile_size, stride)
+    if strategy == "val" and views:
+        n = int(n_pairs)
+        return stride, pos * n, reg * n, [k for k in range(n) for _ in pos]
+    return stride, pos, reg, [0] * len(pos)
+
+
+def batch_bounds(n: int, batch_size: int):
+    """[(k0, k1)] of a DataLoader(batch_size=..., drop_last=False) over n samples in order (the last batch may be ragged)."""
+    return [(k, min(k + int(batch_size), n)) for k in range(0, n, int(batch_size))]
+
+
+def grid_shard(strategy: str, pos, reg, pair_idx, tile_size: int, rows: int, shard=(0, 1)):
+    """This rank's samples of a `grid_samples` list -> (pos, reg, pair_idx, shard_plan).  'test' sweeps are cut into row bands
+    (`band_shards`, the plan SyntheticRasterTiles keeps); a sharded 'val' set is refused."""
+    rank, world = int(shard[0]), int(shard[1])
+    if not 0 <= rank < world:
+        raise ValueError(f"bad shard {tuple(shard)!r}")
+    if strategy != "test":
+        if world > 1:
+            raise ValueError("a sharded validation set is not supported")
+        return list(pos), list(reg), list(pair_idx), None
+    plan = band_shards(pos, tile_size, rows, world)
+    i0, i1 = plan[rank]["i0"], plan[rank]["i1"]
+    return list(pos[i0:i1]), list(reg[i0:i1]), list(pair_idx[i0:i1]), plan

@@ -40,7 +40,7 @@ typedef void* rd_stream_t; /* hipStream_t */
 #define RD_ERR_WS 2
 #define RD_ERR_HIP 3
 
-int rd_version(void); /* 100: r01-r03; 101: rd_set_splitk_workspace registrations belong to (current device, stream); 102: rd_host_register & co; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next / rd_amax, packed operands hold both split forms; 106: rd_plan_*; 107: rd_quant_next_img; 109: rd_assemble_grid_tiles */
+int rd_version(void); /* 100: r01-r03; 101: rd_set_splitk_workspace registrations belong to (current device, stream); 102: rd_host_register & co; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next / rd_amax, packed operands hold both split forms; 106: rd_plan_*; 107: rd_quant_next_img; 109: rd_assemble_grid_tiles; 110: rd_patch_moments, rd_region_moments, rd_assemble_train_patches */
 /* Arithmetic of the split MFMA kernels -- ONE library, chosen per launch (csrc/rd_mfma_dev.h):
  *   6  "split3"   x = x1 + x2 + x3 (three bf16 terms, exact), six products per multiply on v_mfma_f32_32x32x16_bf16.  No
  *                 assumption about the operands; what every launch falls back to.
@@ -494,6 +494,58 @@ int rd_assemble_grid_tiles(const float* dsm_in, const float* dsm_gt, const float
                            int n, int tile, float nodata, int dsm_mode, float dsm_mean, float dsm_std, int ortho_mode,
                            float ortho_mean, float ortho_std, float* input, float* target, uint8_t* mask, float* dsm_mean_out,
                            void* ws, size_t ws_bytes, rd_stream_t s);
+
+/* ---- training set and its normalisation statistics from rasters resident in HBM (train.py:97-161) ------------------- */
+/* out[i*3 ..] = (count, mean, M2 = sum (x - mean)^2) in fp64 over the pixels != nodata (all pixels when !use_nodata) of the
+ * tile x tile patch at pos[i] = (y, x) of one height x width plane: what compute_local_dsm_std_per_centered_patch
+ * (lib/utils.py:111-158) takes per sample in float128 -- std_i = sqrt(M2 / (count - 1)) -- over a batch-1 DataLoader.
+ * Centred: every slab of 8 patch rows is summed, then read again about its own mean; the slabs of a patch are merged in slab
+ * order from (count, sum, M2).  Fixed reduction order, no atomics: a patch's numbers depend on its pixels and `tile` alone (not
+ * on n, its place in the list or the launch shape).  A patch outside the plane reads nothing and gets count 0, NaN, NaN; so
+ * does the mean / M2 of a patch without a valid pixel.  tile: a multiple of 4, at most 1024.  Workspace:
+ * rd_patch_moments_ws_bytes(n, tile).  Kernels: patch_moments_slab, patch_moments_merge. */
+size_t rd_patch_moments_ws_bytes(int n, int tile);
+int rd_patch_moments(const float* plane, int height, int width, const int* pos, int n, int tile, float nodata, int use_nodata,
+                     double* out, void* ws, size_t ws_bytes, rd_stream_t s);
+/* out[0..2] = (count, mean, M2) in fp64 over the union WITH REPETITION of the n_planes x n_rects (plane, rectangle) pairs of a
+ * planar stack of n_stack planes (height x width, plane stride in floats): the pixel set compute_satellite_image_normalization
+ * (lib/utils.py:161-200) concatenates, whose np.mean / np.std are mean and sqrt(M2 / count).  plane_idx [n_planes] and rects
+ * [n_rects][4] = half-open (y0, y1, x0, x1) are HOST arrays.  Every pair is cut into units of whole rows (about 16 K pixels, a
+ * function of the rectangle alone), a unit is summed and read again about its own mean, and one block merges the units in a
+ * fixed order: the result does not depend on the grid.  Workspace: rd_region_moments_ws_bytes(height, width, n_planes, rects,
+ * n_rects) (0 for rectangles the call would refuse).  Kernels: region_moments_units, region_moments_merge. */
+#define RD_REGION_MAX_RECTS 16
+#define RD_REGION_MAX_PLANES 64
+size_t rd_region_moments_ws_bytes(int height, int width, int n_planes, const int* rects, int n_rects);
+int rd_region_moments(const float* planes, long long plane_stride, int n_stack, int height, int width, const int* plane_idx,
+                      int n_planes, const int* rects, int n_rects, double* out, void* ws, size_t ws_bytes, rd_stream_t s);
+/* rd_assemble_patches for a batch whose samples come from SEVERAL rasters (the ConcatDataset of utils.get_dataloader,
+ * lib/utils.py:256-270, over 'train' DsmOrthoDatasets, lib/DsmOrthoDataset.py:161-291).  rasters: DEVICE table of n_rasters
+ * descriptors (ortho = planar stack of n_planes planes; dsm_gt / ortho nullable; ortho_mode 0 = raw radiances, 1 = ortho_mean,
+ * 2 = the sample's mean over its views).  samples: DEVICE int table stored column by column, samples[col * n + i]: col 0
+ * raster id, 1 y, 2 x, 3 aug = k | flip_v << 2 | flip_h << 3, 4 DSM mode (0 raw, 1 the given mean, 2 the patch's mean over
+ * input pixels != nodata), 5 the given DSM mean (float bits), 6-7 the caller's, RD_TRAIN_SAMPLE_INTS + j = plane of view j (the
+ * pair's planes, already permuted).  input[i] = cat(DSM channel if dsm_channel, the views), target / mask as
+ * rd_assemble_patches (nullable together): the same rounding (sub, div as torch's sub_ / div_), mask = gt != 0 && gt != nodata,
+ * augmentation rot90(k) -> flipud -> fliplr.  Patch means come from the fixed-order fp64 sums of rd_patch_sums, so a sample
+ * has the bits rd_patch_sums + rd_assemble_patches give it, whatever its batch mates.  dsm_mean_out[i] = the DSM mean used
+ * (0 for mode 0).  A sample outside its raster, with a bad raster / plane index or mode, or without the raster it needs yields
+ * NaN input / target / dsm_mean and an empty mask and reads nothing.  sums: device scratch of n * 4 doubles.  tile: a multiple
+ * of 4, at most 1024.  Kernels: train_patch_sums, train_patch_write (one launch each for the whole mixed batch). */
+#define RD_TRAIN_SAMPLE_INTS 8
+typedef struct rd_train_raster {
+    const float* dsm_in;
+    const float* dsm_gt;
+    const float* ortho;
+    int height, width, n_planes;
+    float nodata, dsm_std;
+    int ortho_mode;
+    float ortho_mean, ortho_std;
+    int reserved[2];
+} rd_train_raster; /* 64 bytes */
+int rd_assemble_train_patches(const rd_train_raster* rasters, int n_rasters, const int* samples, int n, int views, int dsm_channel,
+                              int tile, float* input, float* target, uint8_t* mask, float* dsm_mean_out, double* sums,
+                              rd_stream_t s);
 
 /* ---- masked residual statistics of a refined DSM (lib/evaluation.py:11-131) ------------------------ */
 /* residual r = raster - gt where raster != nodata, gt != nodata, mask (nullable) != 0 and, if threshold > 0,

@@ -139,6 +139,11 @@ SIGNATURES = {
     "rd_assemble_patches": (I, [P, P, P, LL, P, I, P, P, P, F, P, F, F, I, I, I, P, P, P, P]),
     "rd_assemble_grid_tiles_ws_bytes": (SZ, [I, I]),
     "rd_assemble_grid_tiles": (I, [P, P, P, I, I, I, P, P, I, I, I, I, I, F, I, F, F, I, F, F, P, P, P, P, P, SZ, P]),
+    "rd_patch_moments_ws_bytes": (SZ, [I, I]),
+    "rd_patch_moments": (I, [P, I, I, P, I, I, F, I, P, P, SZ, P]),
+    "rd_region_moments_ws_bytes": (SZ, [I, I, I, P, I]),
+    "rd_region_moments": (I, [P, LL, I, I, I, P, I, P, I, P, P, SZ, P]),
+    "rd_assemble_train_patches": (I, [P, I, P, I, I, I, I, P, P, P, P, P, P]),
     "rd_residual_stats_ws_bytes": (SZ, [LL]),
     "rd_residual_stats": (I, [P, P, P, LL, D, D, P, P, SZ, P]),
     "rd_dilate_mask": (I, [P, P, I, I, I, P]),

@@ -314,3 +314,226 @@ class GpuGridTiles:
                 yield src._hand_over(queue.pop(0))
         while queue:
             yield src._hand_over(queue.pop(0))
+
+
+_RASTER_DESC = [("dsm_in", "<u8"), ("dsm_gt", "<u8"), ("ortho", "<u8"), ("height", "<i4"), ("width", "<i4"), ("n_planes", "<i4"),
+                ("nodata", "<f4"), ("dsm_std", "<f4"), ("ortho_mode", "<i4"), ("ortho_mean", "<f4"), ("ortho_std", "<f4"),
+                ("reserved", "<i4", (2,))]          # rd_train_raster (include/resdepth_hip.h), 64 bytes
+_SAMPLE_INTS = 8                                    # RD_TRAIN_SAMPLE_INTS
+
+
+class TrainSampleSet:
+    """`loader.dataset` of a GpuTrainSet: len() = the samples this rank sees per epoch (what the Trainer's shard checks read),
+    plus the whole sample list (dataset id, positions, pair indices) and the tile size."""
+
+    def __init__(self, tile_size, dataset_id, pos, pair_idx, per_epoch):
+        self.tile_size, self.dataset_id, self.pos, self.pair_idx = int(tile_size), dataset_id, pos, pair_idx
+        self._per_epoch = int(per_epoch)
+
+    def __len__(self):
+        return self._per_epoch
+
+
+class GpuTrainSet:
+    """The training set of the reference (`utils.get_dataloader(cfg_traindata, sampling_strategy='train', ...)`, lib/utils.py:
+    203-272, train.py:146-153) assembled on the GPU from rasters GpuPatchSamplers keep in HBM: per dataset a FIXED list of
+    n_samples patch positions drawn once from its training areas, each bound to an image pair (lib/DsmOrthoDataset.py:316-371,
+    tiling.draw_train_samples: the reference's rule and draw order from `rng`), the lists of several datasets concatenated
+    (ConcatDataset), reshuffled every epoch (tiling.epoch_order), augmented per sample (rot90 / flips, lib/torch_transforms.py)
+    and collated into device-resident batch dicts with the keys of the reference's 'train' sample (:281-291).  A batch may mix
+    rasters: one rd_assemble_train_patches call per batch.  A `trainloader` for resdepth_amd.Trainer: len() = batches per epoch,
+    `.dataset` has a len(), drop_last = False (a ragged last batch, as DataLoader), `batch_size`.
+
+    datasets: [dict(sampler=GpuPatchSampler, area_defn=..., n_samples=..., image_pairs=...)] -- the samplers share tile size,
+    device, view count and either all or none have a ground-truth raster; the DSM std, ortho mean / std and nodata are each
+    sampler's own.  dsm_mean: None (or 0.0) = every patch's own mean.  generator: CPU torch.Generator of the epoch order, the
+    augmentation draws (k, flip_v, flip_h) and the within-pair permutations (lib/DsmOrthoDataset.py:224-227); all of an epoch's
+    draws are made when the epoch starts, so its batches do not depend on batch size or prefetch depth.  shard=(rank, world):
+    this rank's samples of every epoch (equally many per rank).  Batch k + 1 is assembled on a side stream while batch k is
+    consumed (`prefetch`, the hand-over of GpuPatchSampler.stream_batches)."""
+
+    def __init__(self, datasets, input_channels: str, batch_size: int, use_all_stereo_pairs: bool = False,
+                 permute_images_within_pair: bool = False, augment: bool = True, transform_dsm: bool = True,
+                 transform_orthos: bool = True, dsm_mean=None, shuffle: bool = True, generator=None, rng=None, shard=(0, 1),
+                 prefetch: int = 1):
+        import numpy as np
+        if isinstance(datasets, dict):
+            datasets = [datasets]
+        if not datasets:
+            raise ValueError("GpuTrainSet: no datasets")
+        if input_channels not in ("geom",) + _VIEW_CHANNELS:
+            raise ValueError(f"GpuTrainSet: unknown input_channels {input_channels!r}")
+        if int(batch_size) < 1:
+            raise ValueError(f"GpuTrainSet: batch_size must be positive (got {batch_size})")
+        rank, world = int(shard[0]), int(shard[1])
+        if not 0 <= rank < world:
+            raise ValueError(f"GpuTrainSet: bad shard {shard!r}")
+        views = input_channels in _VIEW_CHANNELS
+        samplers = [d.get("sampler") for d in datasets]
+        if not all(isinstance(s, GpuPatchSampler) for s in samplers):
+            raise ValueError("GpuTrainSet: every dataset needs a GpuPatchSampler under 'sampler'")
+        s0 = samplers[0]
+        t = s0.tile
+        if t % 4 or t < 4:
+            raise ValueError(f"GpuTrainSet: tile_size must be a multiple of 4 (got {t})")
+        if any(s.tile != t or s.device != s0.device for s in samplers):
+            raise ValueError("GpuTrainSet: the samplers must share tile size and device")
+        if len({s.dsm_gt is None for s in samplers}) != 1:
+            raise ValueError("GpuTrainSet: either every sampler or none has a ground-truth raster")
+        self.samplers, self.device, self.tile = samplers, s0.device, t
+        self.has_gt = s0.dsm_gt is not None
+        self.input_channels, self.batch_size, self.prefetch = input_channels, int(batch_size), int(prefetch)
+        self.augment, self.permute, self.shuffle = bool(augment), bool(permute_images_within_pair), bool(shuffle)
+        self.generator, self.shard = generator, (rank, world)
+        self.dsm_channel = 0 if input_channels == "stereo" else 1
+        dsm_mode = 0 if not transform_dsm else (2 if not dsm_mean else 1)
+        f32bits = lambda v: int(np.array(v, dtype=np.float32).view(np.int32))       # noqa: E731
+        desc = np.zeros(len(datasets), dtype=_RASTER_DESC)
+        ids, poss, pidx, cols, planes = [], [], [], [], []
+        n_views = None
+        for di, (d, s) in enumerate(zip(datasets, samplers)):
+            area = d["area_defn"]
+            for (x0, x1), (y0, y1) in zip(area["x_extent"], area["y_extent"]):
+                if x0 < 0 or y0 < 0 or x1 >= s.w or y1 >= s.h:
+                    raise ValueError(f"GpuTrainSet: area x {x0}..{x1}, y {y0}..{y1} of dataset {di} is not inside the "
+                                     f"{s.h} x {s.w} raster")
+            pairs = None
+            if views:
+                if s.orthos is None or not d.get("image_pairs"):
+                    raise ValueError(f"GpuTrainSet: input_channels={input_channels!r} needs orthos and image_pairs (dataset {di})")
+                pairs = np.array([[int(p) for p in pr] for pr in d["image_pairs"]], dtype=np.int32)
+                if pairs.ndim != 2 or pairs.shape[1] < 1:
+                    raise ValueError("GpuTrainSet: every image pair must have the same number of views")
+                if pairs.min() < 0 or pairs.max() >= s.orthos.shape[0]:
+                    raise ValueError(f"GpuTrainSet: an image index is outside the {s.orthos.shape[0]} ortho planes (dataset {di})")
+                if n_views not in (None, pairs.shape[1]):
+                    raise ValueError("GpuTrainSet: the datasets must share the number of views per sample")
+                n_views = pairs.shape[1]
+            # the reference's draws, dataset after dataset (each DsmOrthoDataset constructor calls _determine_patches)
+            pos, pi = tiling.draw_train_samples(area, t, d["n_samples"], input_channels, d.get("image_pairs"), use_all_stereo_pairs,
+                                                rng)
+            m = len(pos)
+            ids.append(np.full(m, di, dtype=np.int64))
+            poss.append(pos)
+            pidx.append(pi)
+            c = np.zeros((_SAMPLE_INTS, m), dtype=np.int32)
+            c[0], c[1], c[2], c[4] = di, pos[:, 0], pos[:, 1], dsm_mode
+            c[5] = f32bits(dsm_mean) if dsm_mode == 1 else 0
+            c[6], c[7] = f32bits(s.dsm_std), f32bits(s.nodata)          # the batch dict's per-sample dsm_std / nodata columns
+            cols.append(c)
+            if views:
+                planes.append(pairs[pi])
+            om = s.ortho_mean
+            r = desc[di]
+            r["dsm_in"], r["dsm_gt"] = s.dsm_in.data_ptr(), (s.dsm_gt.data_ptr() if self.has_gt else 0)
+            r["ortho"] = s.orthos.data_ptr() if views else 0
+            r["height"], r["width"], r["n_planes"] = s.h, s.w, (s.orthos.shape[0] if views else 0)
+            r["nodata"], r["dsm_std"], r["ortho_std"] = s.nodata, s.dsm_std, s.ortho_std
+            r["ortho_mode"] = 0 if not transform_orthos else (2 if not om else 1)
+            r["ortho_mean"] = float(om) if r["ortho_mode"] == 1 else 0.0
+        self.views = n_views or 0
+        self._cols = np.concatenate(cols, axis=1)                                        # [8, m], static columns
+        self._planes = np.concatenate(planes, axis=0) if views else np.zeros((self._cols.shape[1], 0), dtype=np.int32)
+        self._ids, self._pos, self._pidx = np.concatenate(ids), np.concatenate(poss), np.concatenate(pidx)
+        m = self._cols.shape[1]
+        self.dataset = TrainSampleSet(t, self._ids, self._pos, self._pidx, (m // world) if world > 1 else m)
+        self.drop_last = False
+        with torch.cuda.device(self.device):
+            self._desc = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(self.device)
+        self._nan = {}
+
+    def __len__(self):
+        return -(-len(self.dataset) // self.batch_size)
+
+    def sample_list(self):
+        """(dataset id int64 [m], positions int64 [m, 2] (y, x), pair indices int64 [m]) of the whole set, in ConcatDataset order."""
+        return self._ids, self._pos, self._pidx
+
+    def table(self, index, aug=None, views=None):
+        """Host sample table (int32 [8 + V, n], the column layout of rd_assemble_train_patches) for the samples `index` of the
+        list; aug: int [n, 3] (k, flip_v, flip_h) or None; views: int [n, V] plane indices replacing the pairs' own order."""
+        import numpy as np
+        idx = np.asarray(index, dtype=np.int64).reshape(-1)
+        tab = np.empty((_SAMPLE_INTS + self.views, idx.size), dtype=np.int32)
+        tab[:_SAMPLE_INTS] = self._cols[:, idx]
+        if self.views:
+            tab[_SAMPLE_INTS:] = (self._planes[idx] if views is None else np.asarray(views, dtype=np.int32).reshape(idx.size, -1)).T
+        if aug is not None:
+            a = np.asarray(aug, dtype=np.int32).reshape(idx.size, 3)
+            tab[3] = a[:, 0] | (a[:, 1] << 2) | (a[:, 2] << 3)
+        return tab
+
+    def assemble(self, index, aug=None, views=None):
+        """The samples `index` of the list as one batch dict (device tensors), on the current stream."""
+        with torch.cuda.device(self.device):
+            return self._assemble(torch.from_numpy(self.table(index, aug, views)))
+
+    def _assemble(self, tab_host):
+        dev, t, v = self.device, self.tile, self.views
+        n = tab_host.shape[1]
+        tab = tab_host.to(dev, non_blocking=True)
+        c = self.dsm_channel + v
+        inp = torch.empty(n, c, t, t, dtype=torch.float32, device=dev)
+        mean = torch.empty(n, dtype=torch.float32, device=dev)
+        sums = torch.empty(n, 4, dtype=torch.float64, device=dev)
+        tgt = msk = None
+        if self.has_gt:
+            tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
+            msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
+        check(load().rd_assemble_train_patches(ptr(self._desc), len(self.samplers), ptr(tab), n, v, self.dsm_channel, t, ptr(inp),
+                                               ptr(tgt), ptr(msk), ptr(mean), ptr(sums), stream_ptr()), "assemble_train_patches")
+        nan = self._nan.get(n)
+        if nan is None:
+            nan = self._nan[n] = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+        batch = {"input": inp, "dsm_mean": mean, "dsm_std": tab[6].view(torch.float32), "nodata": tab[7].view(torch.float32),
+                 "patch_offset_y": tab[1].to(torch.int64), "patch_offset_x": tab[2].to(torch.int64),
+                 "patch_valid_pixels_uly": nan, "patch_valid_pixels_ulx": nan, "patch_valid_pixels_lry": nan,
+                 "patch_valid_pixels_lrx": nan}
+        if tgt is not None:
+            batch["target"], batch["loss_mask"] = tgt, msk.view(torch.bool)
+        return batch
+
+    def epoch_tables(self):
+        """One epoch's draws from `generator` -> [host sample table per batch] (pinned int32 [8 + V, n] each): the order
+        (tiling.epoch_order), then the within-pair permutations, then k, flip_v, flip_h for every sample of the epoch."""
+        import numpy as np
+        g = self.generator
+        order = tiling.epoch_order(self._cols.shape[1], g, self.shard, self.shuffle).numpy()
+        n_e, v = order.size, self.views
+        views = aug = None
+        if self.permute and v > 1:
+            perm = torch.argsort(torch.rand(n_e, v, generator=g), dim=1).numpy()
+            views = np.take_along_axis(self._planes[order], perm, axis=1)
+        if self.augment:
+            aug = torch.stack([torch.randint(0, 4, (n_e,), generator=g), torch.randint(0, 2, (n_e,), generator=g),
+                               torch.randint(0, 2, (n_e,), generator=g)], 1).numpy()
+        tab = self.table(order, aug, views)
+        rows = tab.shape[0]
+        flat = torch.empty(max(tab.size, 1), dtype=torch.int32).pin_memory()
+        out = []
+        for k0, k1 in tiling.batch_bounds(n_e, self.batch_size):
+            piece = flat[k0 * rows:k1 * rows].view(rows, k1 - k0)
+            piece.copy_(torch.from_numpy(np.ascontiguousarray(tab[:, k0:k1])))
+            out.append(piece)
+        return out
+
+    def __iter__(self):
+        tables = self.epoch_tables()
+        src = self.samplers[0]
+        with torch.cuda.device(self.device):
+            side = torch.cuda.Stream(device=self.device)
+        queue = []
+
+        def produce(tab_host):
+            with torch.cuda.device(self.device), torch.cuda.stream(side):
+                b = self._assemble(tab_host)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return b, ev
+
+        for tab_host in tables:
+            queue.append(produce(tab_host))
+            if len(queue) > max(0, self.prefetch):
+                yield src._hand_over(queue.pop(0))
+        while queue:
+            yield src._hand_over(queue.pop(0))

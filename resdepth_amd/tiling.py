@@ -121,3 +121,87 @@ def grid_shard(strategy: str, pos, reg, pair_idx, tile_size: int, rows: int, sha
     plan = band_shards(pos, tile_size, rows, world)
     i0, i1 = plan[rank]["i0"], plan[rank]["i1"]
     return list(pos[i0:i1]), list(reg[i0:i1]), list(pair_idx[i0:i1]), plan
+
+
+# ---- the training set: sampling_strategy 'train' of the reference's `_determine_patches` (lib/DsmOrthoDataset.py:316-371) ----
+def _train_regions(area_defn, tile_size: int):
+    """[(y_start, x_start, n_y, n_x)] per region of `area_defn`: the valid upper-left positions of
+    data_allocation.indices_from_area_defn (lib/data_allocation.py:332-378) -- inclusive extents, every position keeps the
+    tile inside its region."""
+    xe, ye = area_defn["x_extent"], area_defn["y_extent"]
+    if len(xe) != len(ye):
+        raise ValueError("area_defn x_extent / y_extent differ in length")
+    out = []
+    for (x0, x1), (y0, y1) in zip(xe, ye):
+        nx, ny = int(x1) - int(tile_size) + 1 - int(x0) + 1, int(y1) - int(tile_size) + 1 - int(y0) + 1
+        if nx <= 0 or ny <= 0:
+            raise ValueError(f"area x {x0}..{x1}, y {y0}..{y1} does not hold a {tile_size} x {tile_size} tile")
+        out.append((int(y0), int(x0), ny, nx))
+    return out
+
+
+def train_position_count(area_defn, tile_size: int) -> int:
+    """len(indices_from_area_defn(area_defn, tile_size)) without building the list (6e7 entries for an 8192^2 raster)."""
+    return sum(ny * nx for _, _, ny, nx in _train_regions(area_defn, tile_size))
+
+
+def train_position(area_defn, tile_size: int, index):
+    """indices_from_area_defn(area_defn, tile_size)[index] for an int or an integer array `index` -> (y, x) or int64 [m, 2]:
+    regions in order, then y outer, x inner."""
+    import numpy as np
+    regions = _train_regions(area_defn, tile_size)
+    idx = np.asarray(index, dtype=np.int64)
+    flat = idx.reshape(-1)
+    total = sum(ny * nx for _, _, ny, nx in regions)
+    if flat.size and (flat.min() < 0 or flat.max() >= total):
+        raise IndexError(f"train position index outside 0..{total - 1}")
+    out = np.zeros((flat.size, 2), dtype=np.int64)
+    first = 0
+    for y0, x0, ny, nx in regions:
+        sel = (flat >= first) & (flat < first + ny * nx)
+        k = flat[sel] - first
+        out[sel, 0] = y0 + k // nx
+        out[sel, 1] = x0 + k % nx
+        first += ny * nx
+    return (int(out[0, 0]), int(out[0, 1])) if idx.ndim == 0 else out
+
+
+def draw_train_samples(area_defn, tile_size: int, n_samples: int, input_channels: str, image_pairs=None,
+                       use_all_stereo_pairs: bool = False, rng=None):
+    """The sample list of a 'train' DsmOrthoDataset (lib/DsmOrthoDataset.py:316-371) -> (positions int64 [m, 2] (y, x), pair
+    indices int64 [m]) with the reference's rule AND draw order: `rng.choice(count, n_samples, replace=False)` for the
+    positions; only for 'geom-stereo' with more than one pair either every position repeated per pair (use_all_stereo_pairs:
+    m = n_samples * pairs, pair indices 0..P-1 tiled) or `rng.choice(P, n_samples, replace=True)`; every other channel mode
+    gets pair 0 throughout, even with several pairs listed (as the reference).  rng: np.random (default) or a RandomState --
+    after the same np.random.seed the list is the reference's."""
+    import numpy as np
+    rng = np.random if rng is None else rng
+    count = train_position_count(area_defn, tile_size)
+    n_samples = int(n_samples)
+    if not 0 < n_samples <= count:
+        raise ValueError(f"n_samples must be in 1..{count} (the valid patch positions of the area), got {n_samples}")
+    indices = rng.choice(count, n_samples, replace=False)
+    n_pairs = len(image_pairs) if image_pairs else 0
+    if input_channels == "geom-stereo" and n_pairs > 1:
+        if use_all_stereo_pairs:
+            indices = np.repeat(indices, n_pairs)
+            pair_idx = np.tile(np.arange(n_pairs, dtype=np.int64), n_samples)
+        else:
+            pair_idx = np.asarray(rng.choice(n_pairs, n_samples, replace=True), dtype=np.int64)
+    else:
+        pair_idx = np.zeros(n_samples, dtype=np.int64)
+    return train_position(area_defn, tile_size, indices), pair_idx
+
+
+def epoch_order(n: int, generator=None, shard=(0, 1), shuffle: bool = True):
+    """Sample order of one epoch for rank `shard[0]` of `shard[1]`: torch.randperm(n, generator) (the DataLoader's
+    RandomSampler; shuffle=False: 0..n-1), for world > 1 cut to a multiple of world, rank r taking order[r::world] -- every
+    rank gets equally many samples (the Trainer's ragged-batch check needs equal last batches)."""
+    import torch
+    rank, world = int(shard[0]), int(shard[1])
+    if not 0 <= rank < world:
+        raise ValueError(f"bad shard {tuple(shard)!r}")
+    order = torch.randperm(int(n), generator=generator) if shuffle else torch.arange(int(n))
+    if world > 1:
+        order = order[:(int(n) // world) * world][rank::world]
+    return order

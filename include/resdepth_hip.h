@@ -18,6 +18,22 @@
  *    every other shape runs the generic kernels); a depth-d network needs H and W to be multiples of 2^d.  The reference
  *    itself only ever feeds square tiles of 2^k >= 2^(depth+2) pixels (lib/validate_arguments.py:143-171), which is the
  *    rule resdepth_amd.validate_tile_size restates for callers;
+ *  - memory (tests/test_memory_contract_gpu.py holds every entry point to this): a call reads only the tensors it is given and
+ *    writes only its outputs and its scratch, each within the extent its shape (or ws_bytes / part_floats) states.  Outputs and
+ *    scratch need NOT be initialised: a call overwrites every element of an output it produces and never reads scratch it has
+ *    not written -- except what this header asks the caller to zero (magnitude slots before their producer; the split-K
+ *    registration zeroes its own tickets) and the in-place updates (optimizer state, running statistics, the blend raster).  A
+ *    packed weight buffer is opaque: the regions the selected arithmetic does not read stay unwritten.  A BN-statistics buffer
+ *    `part` is written for *rows_out rows of 4*C floats only; rd_conv3x3_last_bwd_data_bnstats and rd_convt_last_bwd_data write
+ *    one row per 16 x 32 image tile and report 0 rows (no statistics epilogue) where that exceeds part_floats.  Alignment:
+ *    every tensor (byte tensors too), scratch and packed buffer 16 bytes (float4 accesses); magnitude slots 128 bytes; the
+ *    split-K registration 256 bytes.
+ *    Scratch sizes that follow a diagnosis knob (rd_tune_set) -- query and call under the SAME knob values:
+ *    rd_conv3x3_last_bwd_weight_ws_bytes (last_blocks, edge_conv); rd_channel_sum_ws_bytes, rd_bn_stats_ws_bytes and
+ *    rd_bn_act_bwd_ws_bytes (rows_blocks); rd_conv3x3_bwd_weight_ws_bytes (wg_strip, wg_blocks, wg_minblocks, tn_tile,
+ *    tn_blocks); rd_convt2x2_bwd_weight_ws_bytes (convt_patch, mfma_f32, tn_tile, tn_blocks); rd_conv1x1_bwd_weight_ws_bytes
+ *    (tn_tile, tn_blocks); rd_conv3x3_first_fwd_stats_ws_bytes and rd_conv3x3_first_bwd_weight_ws_bytes (edge_conv).  A scratch
+ *    smaller than its query is refused (RD_ERR_WS / RD_ERR_ARG) before anything is launched;
  *  - all work is enqueued on `stream` (a hipStream_t); nothing synchronises;
  *  - return 0 on success, non-zero on error; rd_last_error_string() (thread-local)
  *    describes the last failure of the calling thread;
@@ -283,8 +299,9 @@ int rd_conv3x3_last_fwd_tail(const float* z, const float* mean, const float* inv
                              rd_stream_t s);
 /* The head of the backward in one pass over z: the partial sums of rd_conv3x3_last_bwd_weight_tail (wpartial:
  * rd_conv3x3_last_bwd_tail_blocks() rows of 9*C + 9 doubles, finished by rd_tail_wl_finish once C16 is there) AND the BN-backward
- * statistics of level 0 that rd_conv3x3_last_bwd_data_bnstats emits (part / rows_out as there; the data gradient itself is
- * evaluated per element and not stored). */
+ * statistics of level 0 that rd_conv3x3_last_bwd_data_bnstats emits (rows_out as there, but one row per 16 x 32 image tile:
+ * `part` must hold rd_conv3x3_last_bwd_tail_blocks() * 4 * C floats, which is MORE than rd_bn_bwd_part_floats(pixels, C)
+ * wherever the tiles outnumber cdiv(pixels, 64) (small or thin images: 3 x 4 x 4, 1 x 65); the data gradient itself is evaluated per element and not stored). */
 int rd_conv3x3_last_bwd_tail_blocks(int n, int h, int w);
 int rd_conv3x3_last_bwd_tail_fused(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                    float slope, const float* slope_dev, const float* dout, const float* w_last, double* wpartial,

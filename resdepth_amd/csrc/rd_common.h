@@ -128,6 +128,8 @@ int tail_t16_launch(const TailSkip& sk, const float* V, float* t16, long pixels,
 int convt_last_wgrad_launch(const float* x, const TailSkip& sk, const float* dout, const float* wl, float* dwt, double* partial,
                             double* c16, int n, int hc, int wc, int cin, int c0, hipStream_t s);
 int conv_last_tail_blocks(int n, int h, int w);
+// 16 x 32 image tiles of an [n, h, w] tensor: the statistics rows the tile kernels of the last level write (one per tile)
+long edge_tiles(int n, int h, int w);
 int conv_last_bwd_tail_fused_launch(const TailSkip& sk, const float* dout, const float* wl, double* wpartial, float* bn_part, int n,
                                     int h, int w, int c, hipStream_t s);
 int tail_wl_finish_launch(const double* partial, int nb, const double* c16, const float* wt, const float* bt, float* dw, float* dbias,

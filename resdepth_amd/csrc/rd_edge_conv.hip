@@ -1806,6 +1806,8 @@ int conv_last_tail_blocks(int n, int h, int w) {
     return (int)(nt < 1024 ? nt : 1024);
 }
 
+long edge_tiles(int n, int h, int w) { return (long)n * cdiv(w, ET_W) * cdiv(h, ET_H); }
+
 // ---- the head of the backward on the matrix pipe, in exact fp32 (r05; cf. conv_first_wgrad_mfma_kernel) -------------------------------
 // conv_last_bwd_tail_fused_kernel spends 18 of its ~33 vector instructions per element on two sets of nine products: the gradient
 // g = conv_last^T(dout) it evaluates per element, and the last convolution's weight gradient dw[c][tap] += act(BN(z))[p][c] dout[p - off].

@@ -1548,7 +1548,9 @@ int rd_bn_act_bwd_reduce(const float* z, const float* mean, const float* invstd,
     const long rows = pool ? pixels / 4 : pixels;
     RowPlan pl;
     RD_REQUIRE(plan_rows(rows, c, &pl), "rd_bn_act_bwd_reduce: C must be a multiple of 4 and <= 1024 (got %d)", c);
-    const size_t need = (size_t)pl.nb * 4 * c * sizeof(double);
+    // the pooled form uses fewer rows than the query's upper bound; a scratch below the query is refused all the same
+    size_t need = (size_t)pl.nb * 4 * c * sizeof(double);
+    if (const size_t q = rd_bn_act_bwd_ws_bytes(n, h, w, c); q > need) need = q;
     if (!ws || ws_bytes < need) {
         set_error("rd_bn_act_bwd_reduce: workspace too small (%zu < %zu)", ws_bytes, need);
         return RD_ERR_WS;
@@ -1848,7 +1850,11 @@ int rd_conv3x3_last_bwd_data_bnstats(const float* dout, const float* wt, float* 
                "rd_conv3x3_last_bwd_data_bnstats: null pointer");
     RD_REQUIRE(part_floats >= rd_bn_bwd_part_floats((long long)n * h * w, c),
                "rd_conv3x3_last_bwd_data_bnstats: statistics buffer too small");
-    {
+    // the tile kernel writes one row per 16 x 32 image tile: small or thin images (3 x 4 x 4, 1 x 65) have more tiles than the
+    // cdiv(pixels, 64) rows rd_bn_bwd_part_floats counts -- then no statistics epilogue (rows 0), never a store past `part`
+    *rows_out = 0;
+    const size_t tile_floats = (size_t)edge_tiles(n, h, w) * 4 * (size_t)c;
+    if (tile_floats <= part_floats) {
         ProfScope ps((hipStream_t)s, "conv_last_dgrad", 2.0 * n * h * w * 9.0 * c, 4.0 * n * h * w * (double)(2 * c + 1));
         if (int e = conv_last_dgrad_bn_launch(dout, wt, ds, n, h, w, c, bn_z, mean, invstd, gamma, beta, slope, slope_dev, part,
                                               (hipStream_t)s, rows_out))
@@ -1856,6 +1862,9 @@ int rd_conv3x3_last_bwd_data_bnstats(const float* dout, const float* wt, float* 
         if (*rows_out) return RD_OK;
     }
     // channel counts without a tile kernel: plain data gradient, the caller runs the stand-alone reduction
+    RD_REQUIRE(ds || tile_floats <= part_floats,
+               "rd_conv3x3_last_bwd_data_bnstats: ds = NULL (statistics only) needs one row per 16 x 32 image tile: %zu floats in "
+               "`part` (got %zu)", tile_floats, part_floats);
     RD_REQUIRE(ds, "rd_conv3x3_last_bwd_data_bnstats: ds = NULL (statistics only) needs C in {16, 32, 64} (got %d)", c);
     return rd_conv3x3_last_bwd_data(dout, wt, ds, n, h, w, c, s);
 }
@@ -1937,6 +1946,10 @@ int rd_convt_last_bwd_data(const float* dout, const float* V, float* dprev, int 
                          part_floats >= rd_bn_bwd_part_floats((long long)n * hc * wc, cin)),
                "rd_convt_last_bwd_data: statistics hook arguments");
     int rows = 0;
+    // one statistics row per 16 x 32 tile of the coarse grid: where that is more than `part` holds (small or thin images have
+    // more tiles than cdiv(pixels, 64)), the data gradient runs without the epilogue and reports 0 rows -- the caller runs
+    // rd_bn_act_bwd_reduce
+    if (bn_z && (size_t)edge_tiles(n, hc, wc) * 4 * (size_t)cin > part_floats) bn_z = nullptr;
     ProfScope ps((hipStream_t)s, "convt_last_dgrad", 2.0 * n * hc * wc * 16.0 * cin,
                  4.0 * n * hc * wc * (double)(cin * (bn_z ? 2 : 1) + 4));
     if (int e = convt_last_dgrad_launch(dout, V, dprev, n, hc, wc, cin, bn_z, mean, invstd, gamma, beta, slope, slope_dev, part,

@@ -542,14 +542,20 @@ int rd_region_moments(const float* planes, long long plane_stride, int n_stack, 
  * 2 = the sample's mean over its views).  samples: DEVICE int table stored column by column, samples[col * n + i]: col 0
  * raster id, 1 y, 2 x, 3 aug = k | flip_v << 2 | flip_h << 3, 4 DSM mode (0 raw, 1 the given mean, 2 the patch's mean over
  * input pixels != nodata), 5 the given DSM mean (float bits), 6-7 the caller's, RD_TRAIN_SAMPLE_INTS + j = plane of view j (the
- * pair's planes, already permuted).  input[i] = cat(DSM channel if dsm_channel, the views), target / mask as
- * rd_assemble_patches (nullable together): the same rounding (sub, div as torch's sub_ / div_), mask = gt != 0 && gt != nodata,
+ * pair's planes, already permuted).  aug bit 4 (RD_TRAIN_AUG_BOX) marks a sample whose mask is cut to its non-overlap box, as
+ * rd_assemble_grid_tiles' (a 'val' sample, lib/DsmOrthoDataset.py:434-470): the table then has four further columns after the
+ * view planes, RD_TRAIN_SAMPLE_INTS + views + 0..3 = (box_uly, box_ulx, box_lry, box_lrx), inclusive, in coordinates of the
+ * OUTPUT tile (after the augmentation), and mask = inside the box && gt != 0 && gt != nodata; a box that is not inside
+ * 0..tile-1 or has lry < uly or lrx < ulx gives an empty mask.  Only flagged samples read those columns: a table of
+ * RD_TRAIN_SAMPLE_INTS + views columns stays valid while no sample is flagged.  input[i] = cat(DSM channel if dsm_channel, the
+ * views), target / mask as rd_assemble_patches (nullable together): the same rounding (sub, div as torch's sub_ / div_), mask = gt != 0 && gt != nodata,
  * augmentation rot90(k) -> flipud -> fliplr.  Patch means come from the fixed-order fp64 sums of rd_patch_sums, so a sample
  * has the bits rd_patch_sums + rd_assemble_patches give it, whatever its batch mates.  dsm_mean_out[i] = the DSM mean used
  * (0 for mode 0).  A sample outside its raster, with a bad raster / plane index or mode, or without the raster it needs yields
  * NaN input / target / dsm_mean and an empty mask and reads nothing.  sums: device scratch of n * 4 doubles.  tile: a multiple
  * of 4, at most 1024.  Kernels: train_patch_sums, train_patch_write (one launch each for the whole mixed batch). */
 #define RD_TRAIN_SAMPLE_INTS 8
+#define RD_TRAIN_AUG_BOX 16
 typedef struct rd_train_raster {
     const float* dsm_in;
     const float* dsm_gt;

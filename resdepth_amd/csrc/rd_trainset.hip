@@ -272,6 +272,8 @@ __global__ __launch_bounds__(256) void train_patch_sums(const rd_train_raster* _
 
 // grid (sample, output plane, row block): a lane writes four adjacent output pixels (16-byte stores, 4-byte mask stores) and
 // gathers their sources through the inverse of rot90(k) -> flipud -> fliplr; an unrotated, unmirrored row is one 16-byte load
+// aug & RD_TRAIN_AUG_BOX: the mask is cut to the sample's box (columns RD_TRAIN_SAMPLE_INTS + V .. + 3), the 'val' samples of
+// DsmOrthoDataset._get_dsm_loss_mask (lib/DsmOrthoDataset.py:434-470); an unflagged sample never touches those columns
 __global__ __launch_bounds__(256) void train_patch_write(const rd_train_raster* __restrict__ rasters, int n_rasters,
                                                          const int* __restrict__ samples, int n, int V, int dsm_channel, int T,
                                                          const double* __restrict__ sums, int rows_per_block,
@@ -314,6 +316,17 @@ __global__ __launch_bounds__(256) void train_patch_write(const rd_train_raster* 
     const bool fv = (a & 4) != 0, fh = (a & 8) != 0;
     const bool vec = ok && k == 0 && !fh && (W & 3) == 0 && ((uintptr_t)src & 15) == 0;      // every row of the patch 16-B aligned
     const int TQ = T / 4, r0 = rb * rows_per_block, r1 = min(T, r0 + rows_per_block);
+    // the mask's box in output-tile coordinates (inclusive): the whole tile, or the RD_TRAIN_AUG_BOX sample's own columns -- read
+    // by the target plane of a flagged sample only; a box that is not inside the tile is empty
+    int by0 = 0, bx0 = 0, by1 = T - 1, bx1 = T - 1;
+    if (is_target && ok && (a & RD_TRAIN_AUG_BOX)) {
+        const int* bc = samples + (long)(RD_TRAIN_SAMPLE_INTS + V) * n + i;
+        by0 = bc[0];
+        bx0 = bc[n];
+        by1 = bc[2L * n];
+        bx1 = bc[3L * n];
+        if (by0 < 0 || bx0 < 0 || by1 >= T || bx1 >= T || by1 < by0 || bx1 < bx0) { by0 = bx0 = 1; by1 = bx1 = 0; }
+    }
     for (int e = t; e < (r1 - r0) * TQ; e += 256) {
         const int r = r0 + e / TQ, c = (e % TQ) * 4;
         float4 v = make_float4(qnan, qnan, qnan, qnan), o = v;
@@ -345,11 +358,12 @@ __global__ __launch_bounds__(256) void train_patch_write(const rd_train_raster* 
         }
         *reinterpret_cast<float4*>(dst + (long)r * T + c) = o;
         if (is_target) {
+            const bool in_rows = ok && r >= by0 && r <= by1;
             uchar4 m;
-            m.x = ok && v.x != 0.f && v.x != nodata;
-            m.y = ok && v.y != 0.f && v.y != nodata;
-            m.z = ok && v.z != 0.f && v.z != nodata;
-            m.w = ok && v.w != 0.f && v.w != nodata;
+            m.x = in_rows && c >= bx0 && c <= bx1 && v.x != 0.f && v.x != nodata;
+            m.y = in_rows && c + 1 >= bx0 && c + 1 <= bx1 && v.y != 0.f && v.y != nodata;
+            m.z = in_rows && c + 2 >= bx0 && c + 2 <= bx1 && v.z != 0.f && v.z != nodata;
+            m.w = in_rows && c + 3 >= bx0 && c + 3 <= bx1 && v.w != 0.f && v.w != nodata;
             *reinterpret_cast<uchar4*>(mask + (long)i * T * T + (long)r * T + c) = m;
         }
     }

@@ -537,3 +537,206 @@ class GpuTrainSet:
                 yield src._hand_over(queue.pop(0))
         while queue:
             yield src._hand_over(queue.pop(0))
+
+
+_TRAIN_AUG_BOX = 16                                 # RD_TRAIN_AUG_BOX
+_VAL_META = ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
+             "patch_valid_pixels_lrx")
+
+
+class ValSampleSet:
+    """`loader.dataset` of a GpuValSet: len() = the samples this rank reads per epoch (a replicated tail counted on every
+    rank), and per such sample, in loader order, its dataset id, position, non-overlap box, pair index and its `index` in the
+    ConcatDataset; `n_total` = the length of the whole list."""
+
+    def __init__(self, tile_size, stride, index, dataset_id, pos, reg, pair_idx, n_total, shard):
+        self.tile_size, self.stride, self.index = int(tile_size), int(stride), index
+        self.dataset_id, self.pos, self.reg, self.pair_idx = dataset_id, pos, reg, pair_idx
+        self.n_total, self.shard = int(n_total), shard
+
+    def __len__(self):
+        return len(self.index)
+
+
+class GpuValSet:
+    """The validation set of the reference (`utils.get_dataloader(cfg_valdata, 'val', ...)`, lib/utils.py:203-272, train.py:
+    155-161: a ConcatDataset of one 'val' DsmOrthoDataset per entry, read with shuffle=False) assembled on the GPU from rasters
+    GpuPatchSamplers keep in HBM: per dataset the regular grid of its areas with every image pair at every position
+    (tiling.grid_samples), the lists concatenated (tiling.concat_val_samples), each tile's loss mask cut to its non-overlap box
+    (lib/DsmOrthoDataset.py:434-470), collated into device-resident batch dicts with the keys and dtypes of GpuGridTiles in the
+    order and batching of DataLoader(ConcatDataset, batch_size, shuffle=False), ragged last batch included.  A batch may
+    straddle two rasters: one rd_assemble_train_patches call per batch (samples flagged RD_TRAIN_AUG_BOX).  A `valloader` for
+    resdepth_amd.Trainer: len() = batches, `.dataset` has a len(), drop_last = False.
+
+    datasets: [dict(sampler=GpuPatchSampler, area_defn=..., image_pairs=..., dsm_mean=None)] -- the samplers share tile size,
+    device, view count and all have a ground-truth raster; the DSM std, ortho mean / std and nodata are each sampler's own.
+    dsm_mean (per dataset): None (or 0.0) = every tile's own mean over its input pixels != nodata, an fp64 sum rounded once
+    (the bits GpuTrainSet / GpuPatchSampler give the same tile).  shard=(rank, world): `batch_size` is the per-rank size and
+    rank r reads its run of every global batch of batch_size * world samples (tiling.val_shard_batches); a last batch that
+    world does not divide is read whole by every rank, which leaves the globally normalised loss the single-process one.
+    The sample tables are uploaded once; batch k + 1 is assembled on a side stream while batch k is consumed (`prefetch`, the
+    hand-over of GpuPatchSampler.stream_batches)."""
+
+    def __init__(self, datasets, input_channels: str, batch_size: int, shard=(0, 1), prefetch: int = 1,
+                 transform_dsm: bool = True, transform_orthos: bool = True, stride=None, augment: bool = False,
+                 permute_images_within_pair: bool = False):
+        import numpy as np
+        if augment:
+            raise ValueError("GpuValSet: augment=True is not supported (the reference augments 'train' samples only)")
+        if permute_images_within_pair:
+            raise ValueError("GpuValSet: permute_images_within_pair=True is not supported")
+        if isinstance(datasets, dict):
+            datasets = [datasets]
+        if not datasets:
+            raise ValueError("GpuValSet: no datasets")
+        if input_channels not in ("geom",) + _VIEW_CHANNELS:
+            raise ValueError(f"GpuValSet: unknown input_channels {input_channels!r}")
+        if int(batch_size) < 1:
+            raise ValueError(f"GpuValSet: batch_size must be positive (got {batch_size})")
+        rank, world = int(shard[0]), int(shard[1])
+        if not 0 <= rank < world:
+            raise ValueError(f"GpuValSet: bad shard {shard!r}")
+        views = input_channels in _VIEW_CHANNELS
+        samplers = [d.get("sampler") for d in datasets]
+        if not all(isinstance(s, GpuPatchSampler) for s in samplers):
+            raise ValueError("GpuValSet: every dataset needs a GpuPatchSampler under 'sampler'")
+        s0 = samplers[0]
+        t = s0.tile
+        if t % 4 or t < 4:
+            raise ValueError(f"GpuValSet: tile_size must be a multiple of 4 (got {t})")
+        if any(s.tile != t or s.device != s0.device for s in samplers):
+            raise ValueError("GpuValSet: the samplers must share tile size and device")
+        if len({s.dsm_gt is None for s in samplers}) != 1:
+            raise ValueError("GpuValSet: either every sampler or none has a ground-truth raster")
+        if s0.dsm_gt is None:
+            raise ValueError("GpuValSet: a validation set needs the samplers' ground-truth rasters")
+        if stride is not None and not 0 < int(stride) <= t:
+            raise ValueError(f"GpuValSet: stride must be in 1..{t} (got {stride})")
+        self.samplers, self.device, self.tile = samplers, s0.device, t
+        self.input_channels, self.batch_size, self.prefetch = input_channels, int(batch_size), int(prefetch)
+        self.shard = (rank, world)
+        self.dsm_channel = 0 if input_channels == "stereo" else 1
+        f32bits = lambda v: int(np.array(v, dtype=np.float32).view(np.int32))       # noqa: E731
+        desc = np.zeros(len(datasets), dtype=_RASTER_DESC)
+        areas, pair_tabs = [], []
+        n_views = None
+        for di, (d, s) in enumerate(zip(datasets, samplers)):
+            area = d["area_defn"]
+            xe, ye = area["x_extent"], area["y_extent"]
+            if len(xe) != len(ye):
+                raise ValueError(f"GpuValSet: area_defn x_extent / y_extent differ in length (dataset {di})")
+            for (x0, x1), (y0, y1) in zip(xe, ye):
+                if x0 < 0 or y0 < 0 or x1 >= s.w or y1 >= s.h or x1 - x0 + 1 < t or y1 - y0 + 1 < t:
+                    raise ValueError(f"GpuValSet: area x {x0}..{x1}, y {y0}..{y1} of dataset {di} does not hold a {t} x {t} "
+                                     f"tile inside the {s.h} x {s.w} raster")
+            pairs = None
+            if views:
+                if s.orthos is None or not d.get("image_pairs"):
+                    raise ValueError(f"GpuValSet: input_channels={input_channels!r} needs orthos and image_pairs (dataset {di})")
+                rows = [[int(p) for p in pr] for pr in d["image_pairs"]]
+                if len({len(r) for r in rows}) != 1 or not rows[0]:
+                    raise ValueError("GpuValSet: every image pair must have the same number of views")
+                pairs = np.array(rows, dtype=np.int32)
+                if pairs.min() < 0 or pairs.max() >= s.orthos.shape[0]:
+                    raise ValueError(f"GpuValSet: an image index is outside the {s.orthos.shape[0]} ortho planes (dataset {di})")
+                if n_views not in (None, pairs.shape[1]):
+                    raise ValueError("GpuValSet: the datasets must share the number of views per sample")
+                n_views = pairs.shape[1]
+            areas.append((xe, ye, len(pairs) if views else 1))
+            pair_tabs.append(pairs)
+            om = s.ortho_mean
+            r = desc[di]
+            r["dsm_in"], r["dsm_gt"] = s.dsm_in.data_ptr(), s.dsm_gt.data_ptr()
+            r["ortho"] = s.orthos.data_ptr() if views else 0
+            r["height"], r["width"], r["n_planes"] = s.h, s.w, (s.orthos.shape[0] if views else 0)
+            r["nodata"], r["dsm_std"], r["ortho_std"] = s.nodata, s.dsm_std, s.ortho_std
+            r["ortho_mode"] = 0 if not transform_orthos else (2 if not om else 1)
+            r["ortho_mean"] = float(om) if r["ortho_mode"] == 1 else 0.0
+        self.views = v = n_views or 0
+        used_stride, ids, pos, reg, pidx = tiling.concat_val_samples(areas, t, stride, views)
+        ids, pidx = np.array(ids, dtype=np.int64), np.array(pidx, dtype=np.int64)
+        pos, reg = np.array(pos, dtype=np.int64).reshape(-1, 2), np.array(reg, dtype=np.int64).reshape(-1, 4)
+        m = len(ids)
+        # the whole list as the column table of rd_assemble_train_patches: 8 + V + 4 rows (box columns after the view planes)
+        rows = _SAMPLE_INTS + v + 4
+        cols = np.zeros((rows, m), dtype=np.int32)
+        cols[0], cols[1], cols[2], cols[3] = ids, pos[:, 0], pos[:, 1], _TRAIN_AUG_BOX
+        for di, (d, s) in enumerate(zip(datasets, samplers)):
+            sel = ids == di
+            mean = d.get("dsm_mean")
+            mode = 0 if not transform_dsm else (2 if not mean else 1)
+            cols[4, sel] = mode
+            cols[5, sel] = f32bits(mean) if mode == 1 else 0
+            cols[6, sel], cols[7, sel] = f32bits(s.dsm_std), f32bits(s.nodata)
+            if views:
+                cols[_SAMPLE_INTS:_SAMPLE_INTS + v, sel] = pair_tabs[di][pidx[sel]].T
+        cols[_SAMPLE_INTS + v:] = reg.T
+        # this rank's batches, each a contiguous [rows, n] piece of one flat device table (uploaded once)
+        self._bounds = tiling.val_shard_batches(m, self.batch_size, self.shard)
+        index = np.concatenate([np.arange(k0, k1) for k0, k1 in self._bounds]) if self._bounds else np.zeros(0, dtype=np.int64)
+        flat = np.concatenate([np.ascontiguousarray(cols[:, k0:k1]).reshape(-1) for k0, k1 in self._bounds]) \
+            if self._bounds else np.zeros(1, dtype=np.int32)
+        self._rows = rows
+        self._first = np.concatenate([[0], np.cumsum([k1 - k0 for k0, k1 in self._bounds])]).astype(np.int64)
+        self.dataset = ValSampleSet(t, used_stride, index, ids[index], pos[index], reg[index], pidx[index], m, self.shard)
+        self.drop_last = False
+        meta = np.concatenate([pos[index], reg[index]], axis=1)                         # int64 [n_rank, 6]
+        with torch.cuda.device(self.device):
+            self._desc = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(self.device)
+            self._table = torch.from_numpy(flat).to(self.device)
+            self._meta = {k: torch.from_numpy(np.ascontiguousarray(meta[:, c])).to(self.device) for c, k in enumerate(_VAL_META)}
+
+    def __len__(self):
+        return len(self._bounds)
+
+    def sample_list(self):
+        """(dataset id int64 [n], positions int64 [n, 2] (y, x), boxes int64 [n, 4], pair indices int64 [n]) of this rank's
+        samples in loader order."""
+        ds = self.dataset
+        return ds.dataset_id, ds.pos, ds.reg, ds.pair_idx
+
+    def assemble(self, k: int):
+        """Batch k of this loader as one batch dict (device tensors), on the current stream."""
+        with torch.cuda.device(self.device):
+            return self._assemble(int(k))
+
+    def _assemble(self, k):
+        dev, t, v = self.device, self.tile, self.views
+        if not 0 <= k < len(self._bounds):
+            raise ValueError(f"GpuValSet: batch {k} outside 0..{len(self._bounds) - 1}")
+        j0, j1 = int(self._first[k]), int(self._first[k + 1])
+        n = j1 - j0
+        tab = self._table[j0 * self._rows:j1 * self._rows].view(self._rows, n)
+        inp = torch.empty(n, self.dsm_channel + v, t, t, dtype=torch.float32, device=dev)
+        mean = torch.empty(n, dtype=torch.float32, device=dev)
+        sums = torch.empty(n, 4, dtype=torch.float64, device=dev)
+        tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
+        msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
+        check(load().rd_assemble_train_patches(ptr(self._desc), len(self.samplers), tab.data_ptr(), n, v, self.dsm_channel, t,
+                                               ptr(inp), ptr(tgt), ptr(msk), ptr(mean), ptr(sums), stream_ptr()),
+              "assemble_train_patches")
+        batch = {"input": inp, "dsm_mean": mean, "dsm_std": tab[6].view(torch.float32), "nodata": tab[7].view(torch.float32)}
+        for key, col in self._meta.items():
+            batch[key] = col[j0:j1]
+        batch["target"], batch["loss_mask"] = tgt, msk.view(torch.bool)
+        return batch
+
+    def __iter__(self):
+        src = self.samplers[0]
+        with torch.cuda.device(self.device):
+            side = torch.cuda.Stream(device=self.device)
+        queue = []
+
+        def produce(k):
+            with torch.cuda.device(self.device), torch.cuda.stream(side):
+                b = self._assemble(k)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return b, ev
+
+        for k in range(len(self._bounds)):
+            queue.append(produce(k))
+            if len(queue) > max(0, self.prefetch):
+                yield src._hand_over(queue.pop(0))
+        while queue:
+            yield src._hand_over(queue.pop(0))

@@ -108,6 +108,51 @@ def batch_bounds(n: int, batch_size: int):
     return [(k, min(k + int(batch_size), n)) for k in range(0, n, int(batch_size))]
 
 
+def concat_val_samples(areas, tile_size: int, stride: int | None = None, views: bool = True):
+    """Sample list of ConcatDataset([DsmOrthoDataset(d, sampling_strategy='val') ...]) (lib/utils.py:256-270): the
+    `grid_samples(..., 'val', ...)` lists of the datasets one after the other.  areas: [(x_extent, y_extent, n_pairs)] per
+    dataset -> (stride, dataset ids, positions, boxes, pair indices), one entry per sample; a pair index counts within its own
+    dataset's pair list."""
+    ids, pos, reg, pair_idx = [], [], [], []
+    used = int(tile_size) if stride is None else int(stride)
+    for di, (xe, ye, n_pairs) in enumerate(areas):
+        used, p, r, pi = grid_samples(xe, ye, tile_size, "val", stride, n_pairs, views)
+        ids += [di] * len(p)
+        pos += p
+        reg += r
+        pair_idx += pi
+    return used, ids, pos, reg, pair_idx
+
+
+def val_shard_batches(n: int, batch_size: int, shard=(0, 1)):
+    """[(k0, k1)] of rank `shard[0]` of `shard[1]` over a validation list of n samples read in order (shuffle=False,
+    drop_last=False), one entry per batch.  `batch_size` is the PER-RANK size b: a global batch is B = b * world consecutive
+    samples and every rank has ceil(n / B) batches.  Of a full global batch k, rank r takes the contiguous run
+    [k B + r b, k B + (r + 1) b).  A last batch of R = n mod B samples is split evenly (R / world each, in rank order) when
+    world divides R; otherwise EVERY rank takes the whole last batch.
+
+    Why replicate: under the global loss normaliser (GradSync.allreduce_loss_sums, which also assumes equal per-rank batch
+    sizes through numel * world) a replicated batch has both sum |d| and sum mask multiplied by world, so its loss is the
+    single-process one.  The batch grouping of the reference's meter (one loss per global batch, averaged over batches) is
+    kept, no rank idles and no collective is skipped.  world = 1 gives `batch_bounds`."""
+    rank, world = int(shard[0]), int(shard[1])
+    if not 0 <= rank < world:
+        raise ValueError(f"bad shard {tuple(shard)!r}")
+    n, b = int(n), int(batch_size)
+    if b < 1:
+        raise ValueError(f"batch_size must be positive (got {batch_size})")
+    big = b * world
+    out = [(k + rank * b, k + (rank + 1) * b) for k in range(0, n - n % big, big)]
+    rest = n % big
+    if rest:
+        k = n - rest
+        if rest % world == 0:
+            out.append((k + rank * (rest // world), k + (rank + 1) * (rest // world)))
+        else:
+            out.append((k, n))
+    return out
+
+
 def grid_shard(strategy: str, pos, reg, pair_idx, tile_size: int, rows: int, shard=(0, 1)):
     """This rank's samples of a `grid_samples` list -> (pos, reg, pair_idx, shard_plan).  'test' sweeps are cut into row bands
     (`band_shards`, the plan SyntheticRasterTiles keeps); a sharded 'val' set is refused."""

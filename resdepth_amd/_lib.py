@@ -423,6 +423,14 @@ def workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
     return buf
 
 
+def workspaces_of(stream: "torch.cuda.Stream") -> list:
+    """The scratch buffers keyed by `stream` right now.  Whoever keeps raw pointers into them beyond the stream's own order
+    (a captured graph, a launch plan) holds these references: workspace() then cannot hand the memory back while they last."""
+    key = (stream.device.index, stream.cuda_stream)
+    with _ws_lock:
+        return [buf for k, buf in _ws.items() if k[:2] == key]
+
+
 _splitk = {}
 _splitk_clock = 0
 # the most a launch uses: tiles * ranges <= 1024 partial tiles of 128 x 64 floats (csrc/rd_igemm.hip launch_nt) + 64 KB of tickets

@@ -46,6 +46,8 @@ class GraphedTrainStep:
         self._one = None
         self.why_eager = None                    # reason the last call ran eagerly (None: it was a replay)
         self.replays = 0
+        self.recordings = 0                      # captures / plan recordings completed so far (a dropped one is captured again)
+        self._ws_held = None                     # the side stream's scratch buffers the captured kernels point into
 
     # ---- the eager iteration (lib/Trainer.py:212-222) -------------------------------------------------------------------
     def _eager(self, x, y, mask, mean, std):
@@ -70,6 +72,8 @@ class GraphedTrainStep:
         pass
 
     def _replay(self):
+        """-> None after a replay.  A variant that had to DROP its capture during this call and ran the iteration eagerly
+        instead returns that iteration's loss (and has set `why_eager` and left `p.grad` as `keep_grads` asks)."""
         self._graph.replay()
 
     def _eligible(self, x):
@@ -94,7 +98,7 @@ class GraphedTrainStep:
 
     def invalidate(self):
         """Drop the captured graph (the next eligible call captures again)."""
-        self._graph = self._static = self._loss = self._grads = self._key = self._cap_token = None
+        self._graph = self._static = self._loss = self._grads = self._key = self._cap_token = self._ws_held = None
 
     def __del__(self):
         try:
@@ -136,6 +140,10 @@ class GraphedTrainStep:
         self._grads = [p.grad for p in self.params]
         self._key = self._shape_key(batch)
         self._cap_token = self.optimizer._cap
+        # the weight-gradient stream is shared with the eager backward, and _lib.workspace() REPLACES a scratch buffer that a
+        # larger eager batch finds too small: the captured kernels keep the raw pointers, so the buffers stay alive with them
+        side = getattr(self.model, "_side_stream", None)
+        self._ws_held = _lib.workspaces_of(side) if side is not None else []
 
     def __call__(self, x, y, mask, mean, std):
         """-> the iteration's loss as a 0-dim device tensor.  After a replay it is the graph's own output buffer: read it (or
@@ -177,12 +185,15 @@ class GraphedTrainStep:
                     self.why_eager = "capture preparation"
                     return loss
                 self._capture(batch)
+                self.recordings += 1
             else:
                 # the new batch into the static input buffers: one launch for all of them (five blit kernels were 55 us at the head
                 # of every step, in front of the first convolution)
                 _lib.copy_segments([(s, t) for s, t in zip(self._static, batch) if s.data_ptr() != t.data_ptr()])
             self.optimizer.advance()
-            self._replay()
+            taken = self._replay()
+            if taken is not None:
+                return taken                     # the capture was dropped and the eager iteration took this call
             self.replays += 1
             self.why_eager = None
             if self.keep_grads:

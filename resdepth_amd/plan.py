@@ -18,7 +18,16 @@ The captured hipGraph itself is never launched; it only owns the memory.  Everyt
 memory (graph.py: the static batch tensors, Adam's scalar block).  The FIRST replay is verified: the same batch runs once
 eagerly and once through the plan from the same state, and parameters, moments, BatchNorm buffers and loss must agree bit for
 bit -- a kernel the recorder cannot see (a torch op inside the iteration) would show up there, and the plan is then dropped for
-good (`why_eager`).
+good (`why_eager`, `plan_rejected`): that call returns the eager iteration's loss and leaves its gradients as `keep_grads`
+asks, it is not counted in `replays`, and every later call runs eagerly.  A recording that cannot become a plan (poisoned by
+the library, or an exception inside the capture) executed nothing: the eager iteration takes that call too, after the
+packed-weight cache the recording's forward filled in -- without running a pack kernel -- has been dropped.
+
+The recorder sees the library's launches only, so the batch reaches the iteration in the form the loss wants (`_canonical`:
+fp32 contiguous input / target / mean / std, a uint8 mask); whatever conversion a batch needs runs as ordinary torch kernels
+BEFORE the recorded region, and such a batch replays like any other.  `recordings` counts the recordings completed so far
+(1 + the number of times a plan was dropped and recorded again: optimizer.load_state_dict, re-homed parameters).  The
+weight-gradient stream's scratch buffers a plan points into are held by the step (`_ws_held`) for as long as the plan lives.
 
 lib/Trainer.py:159-179,212-222 is the loop this replaces."""
 from __future__ import annotations
@@ -49,6 +58,7 @@ class PlannedTrainStep(GraphedTrainStep):
         self._rec = None
         self.verify = verify
         self._verified = False
+        self.plan_rejected = None                # why the plan was given up for good (None: it was not)
         self.n_launches = self.n_segments = 0
 
     # ---- eligibility: data parallelism is fine (host actions); what runs torch ops inside the iteration is not ----------------
@@ -76,6 +86,20 @@ class PlannedTrainStep(GraphedTrainStep):
         if _lib.prof_level_py() != 0:
             return "the per-kernel profiler is on"
         return None
+
+    @staticmethod
+    def _canonical(batch):
+        """The batch as loss._prep / UNet.forward would convert it INSIDE the iteration -- the same torch ops, so the same
+        bits -- done here, outside the recorded region: a plan does not hold torch's kernels.  Nothing is launched for a batch
+        that is in this form already (bool masks are re-viewed)."""
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in batch):
+            return batch                         # __call__ reports it
+        x, y, mask, mean, std = batch
+        x = x.contiguous().float()
+        y = y.to(torch.float32).contiguous()
+        if mask.dtype != torch.uint8:
+            mask = (mask != 0).to(torch.uint8) if mask.dtype != torch.bool else mask.view(torch.uint8)
+        return x, y, mask.contiguous(), mean.to(torch.float32).contiguous(), std.to(torch.float32).contiguous()
 
     def invalidate(self):
         super().invalidate()
@@ -132,12 +156,14 @@ class PlannedTrainStep(GraphedTrainStep):
             # allocator or runtime error): the recording executed nothing, so the eager iteration can take this call
             _lib._plan_rec = None
             self.invalidate()
+            self.model.invalidate_packed()       # the recording's forward marked the packed weights current; no pack kernel ran
             self.warmup = 1 << 62
             raise _PlanUnavailable(f"the recording raised {type(e).__name__}: {str(e)[:200]}") from e
         if self._plan is None:
             # the iteration holds something a plan cannot: stay eager from now on (the hipGraph of the capture is dropped too)
             why = self._plan_error
             self.invalidate()
+            self.model.invalidate_packed()       # as above
             self.warmup = 1 << 62
             raise _PlanUnavailable(why)
 
@@ -203,18 +229,24 @@ class PlannedTrainStep(GraphedTrainStep):
             flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=self._static[0].device if dist.get_backend(gs.pg) == "nccl" else "cpu")
             dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=gs.pg)
             ok = bool(int(flag))
-        for p in self.params:
-            p.grad = None
-        self._loss.copy_(want[-1])               # the state now is the eager iteration's (identical when ok)
-        self.model.invalidate_packed()
+        self.model.invalidate_packed()           # the state now is the eager iteration's (identical when ok)
         if not ok:
+            # this call was the eager reference pass: its loss, and -- keep_grads -- its gradients, as _eager leaves them
+            if not self.keep_grads:
+                for p in self.params:
+                    p.grad = None
+            taken = want[-1].clone()
             self.invalidate()
             self.warmup = 1 << 62
-            self.plan_rejected = "the first replay did not reproduce the eager iteration bit for bit"
-            return
+            self.why_eager = self.plan_rejected = "the first replay did not reproduce the eager iteration bit for bit"
+            return taken
+        for p in self.params:
+            p.grad = None
+        self._loss.copy_(want[-1])
         self._verified = True
 
     def __call__(self, x, y, mask, mean, std):
+        x, y, mask, mean, std = self._canonical((x, y, mask, mean, std))
         try:
             out = super().__call__(x, y, mask, mean, std)
         except _PlanUnavailable as e:

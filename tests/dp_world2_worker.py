@@ -131,6 +131,8 @@ def main():
     ap.add_argument("--tune", default="", help="RD_TUNE string (kernel-selection knobs), applied before the library loads")
     ap.add_argument("--ragged", type=int, default=0)
     ap.add_argument("--plan", type=int, default=0, help="mode plan: 1 = replay the iteration from a launch plan, 0 = eager")
+    ap.add_argument("--reject-rank", type=int, default=-1,
+                    help="mode plan: on this rank only, the first run of the plan leaves one wrong bit in a parameter")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     if a.tune:
@@ -205,6 +207,15 @@ def main():
             dp.broadcast_parameters(model, 0)
             opt = FusedAdam(model.parameters(), lr=2e-4, weight_decay=1e-5)
             step_fn = PlannedTrainStep(model, opt, warmup=1 if a.plan else 1 << 60)
+            if a.reject_rank == a.rank:
+                run_plan, runs = step_fn._run_plan, [0]
+
+                def perturbed():
+                    run_plan()
+                    runs[0] += 1
+                    if runs[0] == 1:         # the verification's MIN all-reduce must make the OTHER rank drop its plan too
+                        model._flat_param[:1].view(torch.int32).bitwise_xor_(1)
+                step_fn._run_plan = perturbed
             shards = []
             for k in range(2):
                 b = dp.shard_batch(make_batch(a.batch, k, a.tile, ARCH[a.arch]["n_input_channels"]), a.rank, a.world)

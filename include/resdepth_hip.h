@@ -87,6 +87,9 @@ int rd_mfma_products(void);
  *     -> dx, rd_convt2x2_fwd* -> out, rd_bn_act_pool_fwd -> a (un-pooled form), rd_bn_act_bwd_apply -> dz), out2 = slot of
  *     the pooled output (rd_conv3x3_fwd_act, rd_bn_act_pool_fwd, rd_conv3x3_first_fwd_act); rd_pack_*: out2 = the weight's
  *     slot, which the call fills itself before it writes the three-product form of the operand.
+ *     Launches that have no split kernel at all take no three-product form on any operands and ignore a and b (out / out2 are
+ *     still committed): a transposed-convolution forward of Cin <= 128 that the patch kernel refuses (exact-f32 row tiles) and a
+ *     weight gradient on the generic TN kernel with a tile other than 128 x 128 (a side of its GEMM output of at most 64; exact-f32).
  *   rd_amax(x, n, slot): max |x[0..n)| into a (zeroed) slot: operands that no producer of this library wrote. */
 int rd_quant_next(const unsigned* a_amax, const unsigned* b_amax, unsigned* out_amax, unsigned* out2_amax);
 /* Per-IMAGE slots (inference, r06): a, out and out2 are arrays of slots, one per image of the batch, `img_stride_words` 32-bit

@@ -158,6 +158,11 @@ SIGNATURES = {
     "rd_prof_reset": (I, []),
     "rd_prof_collect": (I, [P, I]),
 }
+# include/resdepth_hip_tta.h (test-time augmentation), one to one as above; to be folded into SIGNATURES with that header
+SIGNATURES_TTA = {
+    "rd_blend_accumulate_tta": (I, [P, P, P, P, P, P, I, I, I, I, P, I, I, P]),
+    "rd_assemble_grid_tiles_aug": (I, [P, P, P, I, I, I, P, P, I, I, I, I, I, F, I, F, F, I, F, F, P, P, P, P, P, P, SZ, P]),
+}
 
 
 class ProfEntry(C.Structure):
@@ -178,7 +183,7 @@ def load():
                 f"resdepth_amd: HIP library not built ({LIB_PATH} missing). Run resdepth_amd/csrc/build.sh; "
                 "there is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -1064,6 +1064,105 @@ __global__ __launch_bounds__(256) void blend_batch_kernel(const float* __restric
     raster[(long)y * cols + x] = acc;
 }
 
+// ---- test-time augmentation: the square's symmetry group on a T x T tile ------------------------------------------------
+// Code a = k | flip_v << 2 | flip_h << 3 = rot90(k) -> flipud -> fliplr (lib/torch_transforms.py, assemble_patches_kernel).
+// aug_src: the plain-tile pixel (sr, sc) that the oriented tile shows at (r, c); aug_dst is its inverse.  Both map an
+// axis-aligned rectangle onto an axis-aligned rectangle (sides swapped for odd k), which is what the staging below relies on.
+__device__ __forceinline__ void aug_src(int a, int T, int r, int c, int& sr, int& sc) {
+    const int k = a & 3, c1 = (a & 8) ? T - 1 - c : c, r1 = (a & 4) ? T - 1 - r : r;
+    if (k == 0) { sr = r1; sc = c1; }
+    else if (k == 1) { sr = c1; sc = T - 1 - r1; }
+    else if (k == 2) { sr = T - 1 - r1; sc = T - 1 - c1; }
+    else { sr = T - 1 - c1; sc = r1; }
+}
+__device__ __forceinline__ void aug_dst(int a, int T, int sr, int sc, int& r, int& c) {
+    const int k = a & 3;
+    int r1, c1;
+    if (k == 0) { r1 = sr; c1 = sc; }
+    else if (k == 1) { c1 = sr; r1 = T - 1 - sc; }
+    else if (k == 2) { r1 = T - 1 - sr; c1 = T - 1 - sc; }
+    else { c1 = T - 1 - sr; r1 = sc; }
+    r = (a & 4) ? T - 1 - r1 : r1;
+    c = (a & 8) ? T - 1 - c1 : c1;
+}
+
+// rd_blend_accumulate_tta: blend_batch_kernel for oriented predictions.  Block (tile i = first + blockIdx.y, 32 x 32 cell of
+// it); a thread holds four raster pixels of the cell (one column, rows 8 apart) and OWNS a pixel iff no tile first <= j < i
+// covers it; owners add the tiles j = i .. last - 1 that cover the pixel, in order -- the per-pixel order of
+// blend_batch_kernel, no atomics.  The block walks j together: the part of pred[j] that lands on the cell is an axis-aligned
+// rectangle of pred[j] (<= 32 x 32), read row by row into LDS (128-B runs whatever the orientation) and picked up through
+// aug_dst.  LDS row stride 33 dwords: lanes of a row differ in the LDS column (even k) or the LDS row (odd k), either way
+// 32 distinct banks for ds_read_b32 / ds_write_b32.  Raster: 32 doubles = 256-B runs per row, read once and written once.
+constexpr int TTA_CELL = 32;
+
+// acc + den * w * scale in ONE rounding: the blend kernels above compile `acc += (double)den * w` to v_fmac_f64 (-ffp-contract=on),
+// and den * scale (a power of two) is exact -- so this is scale x their step, bit for bit, whatever the compiler contracts here
+__device__ __forceinline__ double blend_tta_add(double acc, float den, double w, double scale) {
+    return fma((double)den * scale, w, acc);
+}
+
+__global__ __launch_bounds__(256) void blend_tta_kernel(const float* __restrict__ pred, const float* __restrict__ mean,
+                                                        const float* __restrict__ stdv, const int* __restrict__ pos,
+                                                        const int* __restrict__ reg, const int* __restrict__ aug, int first,
+                                                        int last, int T, int stride, double scale,
+                                                        double* __restrict__ raster, int rows, int cols) {
+    __shared__ float stage[TTA_CELL * (TTA_CELL + 1)];
+    const int i = first + blockIdx.y, t = threadIdx.x;
+    const int cells = (T + TTA_CELL - 1) / TTA_CELL;
+    const int R0 = (blockIdx.x / cells) * TTA_CELL, C0 = (blockIdx.x % cells) * TTA_CELL;
+    const int Y0 = pos[i * 2] + R0, X0 = pos[i * 2 + 1] + C0;                       // the cell's raster rectangle
+    const int h = min(TTA_CELL, T - R0), w = min(TTA_CELL, T - C0);
+    const int lc = t & 31, lr = t >> 5, x = X0 + lc;
+    bool own[4];
+    double acc[4];
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int y = Y0 + lr + 8 * q;
+        own[q] = lc < w && lr + 8 * q < h && (unsigned)y < (unsigned)rows && (unsigned)x < (unsigned)cols;
+        for (int j = first; own[q] && j < i; ++j)
+            if ((unsigned)(y - pos[j * 2]) < (unsigned)T && (unsigned)(x - pos[j * 2 + 1]) < (unsigned)T) own[q] = false;
+        acc[q] = own[q] ? raster[(long)y * cols + x] : 0.0;
+        any = any || own[q];
+    }
+    if (!__syncthreads_or(any)) return;
+    const int overlap = T - stride;
+    const double step = overlap > 1 ? 1.0 / (double)(overlap - 1) : 0.0;
+    for (int j = i; j < last; ++j) {
+        const int yj = pos[j * 2], xj = pos[j * 2 + 1];
+        // the cell's part of tile j, in tile j's plain coordinates [a0, a1) x [b0, b1): uniform over the block
+        const int a0 = max(Y0 - yj, 0), a1 = min(Y0 + h - yj, T), b0 = max(X0 - xj, 0), b1 = min(X0 + w - xj, T);
+        if (a0 >= a1 || b0 >= b1) continue;
+        const int a = aug ? aug[j] & 15 : 0;
+        int p0, q0, p1, q1;
+        aug_dst(a, T, a0, b0, p0, q0);
+        aug_dst(a, T, a1 - 1, b1 - 1, p1, q1);
+        const int pr = min(p0, p1), pc = min(q0, q1), ph = abs(p1 - p0) + 1, pw = abs(q1 - q0) + 1;
+        __syncthreads();                                   // the previous tile's picks are done
+        const float* src = pred + (long)j * T * T;
+        for (int e = t; e < ph * pw; e += 256) {
+            const int er = e / pw, ec = e - er * pw;
+            stage[er * (TTA_CELL + 1) + ec] = src[(long)(pr + er) * T + pc + ec];
+        }
+        __syncthreads();
+        const float sj = stdv[j], mj = mean[j];
+        const int uly = reg[j * 4], ulx = reg[j * 4 + 1], lry = reg[j * 4 + 2], lrx = reg[j * 4 + 3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int rj = Y0 + lr + 8 * q - yj, cj = x - xj;
+            if (!own[q] || rj < a0 || rj >= a1 || cj < b0 || cj >= b1) continue;
+            int r, c;
+            aug_dst(a, T, rj, cj, r, c);
+            const double wgt = blend_axis(rj, uly, lry, T, overlap, step) * blend_axis(cj, ulx, lrx, T, overlap, step);
+            const float den = __fadd_rn(__fmul_rn(stage[(r - pr) * (TTA_CELL + 1) + c - pc], sj), mj);
+            acc[q] = blend_tta_add(acc[q], den, wgt, scale);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (own[q]) raster[(long)(Y0 + lr + 8 * q) * cols + x] = acc[q];
+}
+
 // ---- bilinear 2x upsampling (up_mode='bilinear', lib/UNet.py:20) ---------------------------------------------
 // nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False): src = max(0.5*(dst+0.5)-0.5, 0), i0 = floor(src),
 // i1 = i0 + (i0 < size-1), l1 = src - i0, l0 = 1 - l1   (same arithmetic as ATen's upsample_bilinear2d).
@@ -1381,6 +1480,71 @@ __global__ __launch_bounds__(256) void grid_tile_write(
             m.w = row_in && c + 3 >= g.b_ulx && c + 3 <= g.b_lrx && v.w != 0.f && v.w != nodata;
             *reinterpret_cast<uchar4*>(mask + (long)i * T * T + (long)r * T + c) = m;
         }
+    }
+}
+
+// rd_assemble_grid_tiles_aug: grid_tile_write for prediction tiles in a given orientation (no target / mask).  The means are
+// grid_tile_write's (the slab partials of grid_tile_sums over the untransformed pixels, in slab order), every pixel goes
+// through the same sub / div, so an oriented tile is the permutation of the plain one bit for bit.  Block (sample, plane,
+// GRID_AUG_CELL^2 cell of the OUTPUT tile): the cell's source is an axis-aligned rectangle of the raster (sides swapped for odd
+// k), read row by row (256-B runs) into LDS and written out row by row through aug_src (256-B runs).  LDS row stride 65
+// dwords: the lanes of an output row differ in the LDS column (even k) or the LDS row (odd k) -- 32 distinct banks per half
+// wave either way.
+constexpr int GRID_AUG_CELL = 64;
+
+__global__ __launch_bounds__(256) void grid_tile_write_aug(
+    const float* __restrict__ dsm_in, const float* __restrict__ ortho, long plane_stride, int H, int W, int n_planes,
+    const int* __restrict__ samples, const int* __restrict__ pair_planes, int n_pairs, int V, int dsm_channel, int T, int S,
+    int dsm_mode, float dsm_mean_fixed, float dsm_std, int ortho_mode, float ortho_mean_fixed, float ortho_std,
+    const double* __restrict__ ws, const int* __restrict__ aug, float* __restrict__ input, float* __restrict__ dsm_mean_out) {
+    __shared__ float stage[GRID_AUG_CELL * (GRID_AUG_CELL + 1)];
+    const int i = blockIdx.x, p = blockIdx.y, t = threadIdx.x;
+    const int C = dsm_channel + V;
+    const GridSample g = grid_sample(samples, i, pair_planes, n_pairs, V, n_planes, H, W, plane_stride, T, 0);
+    float dmean = dsm_mode == 1 ? dsm_mean_fixed : 0.f;
+    float omean = ortho_mode == 1 ? ortho_mean_fixed : 0.f;
+    if (dsm_mode == 2) {
+        double s = 0.0, c = 0.0;
+        for (int k = 0; k < S; ++k) {
+            s += ws[((long)i * S + k) * 4];
+            c += ws[((long)i * S + k) * 4 + 1];
+        }
+        dmean = (float)(s / c);
+    }
+    if (ortho_mode == 2 && V > 0 && p >= dsm_channel) {
+        double s = 0.0;
+        for (int k = 0; k < S; ++k) s += ws[((long)i * S + k) * 4 + 2];
+        omean = (float)(s / ((double)V * T * T));
+    }
+    if (p == 0 && blockIdx.z == 0 && t == 0) dsm_mean_out[i] = g.ok ? dmean : __int_as_float(0x7fc00000);
+    const bool is_dsm = p < dsm_channel;
+    const float* src = is_dsm ? dsm_in : (g.ok ? ortho + (long)pair_planes[g.pair * V + p - dsm_channel] * plane_stride : ortho);
+    const float mean = is_dsm ? dmean : omean, sdv = is_dsm ? dsm_std : ortho_std;
+    const int mode = is_dsm ? dsm_mode : ortho_mode;
+    float* dst = input + ((long)i * C + p) * T * T;
+    const int cells = (T + GRID_AUG_CELL - 1) / GRID_AUG_CELL;
+    const int R0 = (blockIdx.z / cells) * GRID_AUG_CELL, C0 = (blockIdx.z % cells) * GRID_AUG_CELL;
+    const int h = min(GRID_AUG_CELL, T - R0), w = min(GRID_AUG_CELL, T - C0);
+    const int a = aug ? aug[i] & 15 : 0;
+    int p0, q0, p1, q1;
+    aug_src(a, T, R0, C0, p0, q0);
+    aug_src(a, T, R0 + h - 1, C0 + w - 1, p1, q1);
+    const int sr0 = min(p0, p1), sc0 = min(q0, q1), sh = abs(p1 - p0) + 1, sw = abs(q1 - q0) + 1;
+    if (g.ok) {
+        // no loop vectoriser: it pairs the sub of two iterations into v_pk_add_f32 (csrc/build.sh: no packed-f32 VALU anywhere)
+#pragma clang loop vectorize(disable)
+        for (int e = t; e < sh * sw; e += 256) {
+            const int er = e / sw, ec = e - er * sw;
+            const float v = src[(long)(g.uly + sr0 + er) * W + g.ulx + sc0 + ec];
+            stage[er * (GRID_AUG_CELL + 1) + ec] = mode ? __fdiv_rn(__fsub_rn(v, mean), sdv) : v;
+        }
+    }
+    __syncthreads();
+    for (int e = t; e < h * w; e += 256) {
+        const int er = e / w, ec = e - er * w;
+        int sr, sc;
+        aug_src(a, T, R0 + er, C0 + ec, sr, sc);
+        dst[(long)(R0 + er) * T + C0 + ec] = g.ok ? stage[(sr - sr0) * (GRID_AUG_CELL + 1) + sc - sc0] : __int_as_float(0x7fc00000);
     }
 }
 
@@ -2124,6 +2288,28 @@ int rd_blend_accumulate(const float* pred, const float* mean, const float* stdv,
     return RD_OK;
 }
 
+int rd_blend_accumulate_tta(const float* pred, const float* mean, const float* stdv, const int* pos, const int* reg,
+                            const int* aug, int n, int tile_size, int stride, int log2_variants, double* raster, int rows,
+                            int cols, rd_stream_t s) {
+    RD_REQUIRE(pred && mean && stdv && pos && reg && raster, "rd_blend_accumulate_tta: null pointer");
+    RD_REQUIRE(n > 0 && tile_size > 0 && stride > 0 && stride <= tile_size && rows > 0 && cols > 0,
+               "rd_blend_accumulate_tta: bad shape (n=%d tile=%d stride=%d raster=%dx%d)", n, tile_size, stride, rows, cols);
+    RD_REQUIRE(log2_variants >= 0 && log2_variants <= 4, "rd_blend_accumulate_tta: log2_variants must be in 0..4 (got %d)",
+               log2_variants);
+    ProfScope ps((hipStream_t)s, "blend_accumulate_tta", 0, 20.0 * n * tile_size * tile_size);
+    const int cells = cdiv(tile_size, TTA_CELL);
+    const double scale = 1.0 / (double)(1 << log2_variants);
+    // launches of up to 64 samples, in order: within one the owner threads walk the covering samples in order, and a later
+    // launch adds after an earlier one -- rd_blend_accumulate's per-pixel order for any n
+    for (int first = 0; first < n; first += 64) {
+        const int last = first + 64 < n ? first + 64 : n;
+        RD_LAUNCH(blend_tta_kernel, dim3(cells * cells, last - first), dim3(256), 0, (hipStream_t)s, pred, mean, stdv, pos, reg,
+                  aug, first, last, tile_size, stride, scale, raster, rows, cols);
+    }
+    RD_LAUNCH_CHECK("blend_accumulate_tta");
+    return RD_OK;
+}
+
 int rd_patch_sums(const float* planes, long long plane_stride, const int* plane_idx, int p_per_patch, const int* pos,
                   int n, int tile, int width, float nodata, int use_nodata, double* sums, rd_stream_t s) {
     RD_REQUIRE(planes && plane_idx && pos && sums && n > 0 && tile > 0 && width >= tile && p_per_patch > 0,
@@ -2197,6 +2383,46 @@ int rd_assemble_grid_tiles(const float* dsm_in, const float* dsm_gt, const float
               nodata, dsm_mode, dsm_mean, dsm_std, ortho_mode, ortho_mean, ortho_std, aligned, (const double*)ws, rows_per_block,
               input, target, mask, dsm_mean_out);
     RD_LAUNCH_CHECK("grid_tile_write");
+    return RD_OK;
+}
+
+int rd_assemble_grid_tiles_aug(const float* dsm_in, const float* dsm_gt, const float* ortho_planes, int n_planes, int height,
+                               int width, const int* samples, const int* pair_planes, int n_pairs, int views, int dsm_channel,
+                               int n, int tile, float nodata, int dsm_mode, float dsm_mean, float dsm_std, int ortho_mode,
+                               float ortho_mean, float ortho_std, const int* aug, float* input, float* target, uint8_t* mask,
+                               float* dsm_mean_out, void* ws, size_t ws_bytes, rd_stream_t s) {
+    RD_REQUIRE(!target && !mask, "rd_assemble_grid_tiles_aug: oriented tiles are for prediction, target / mask must be null");
+    RD_REQUIRE(dsm_in && samples && input && dsm_mean_out && n > 0 && height >= tile && width >= tile && views >= 0,
+               "rd_assemble_grid_tiles_aug: bad arguments");
+    RD_REQUIRE(tile >= GRID_SLAB_ROWS && tile % GRID_SLAB_ROWS == 0,
+               "rd_assemble_grid_tiles_aug: tile must be a positive multiple of %d (got %d)", GRID_SLAB_ROWS, tile);
+    RD_REQUIRE((dsm_channel == 0 || dsm_channel == 1) && dsm_channel + views >= 1, "rd_assemble_grid_tiles_aug: no input channel");
+    RD_REQUIRE(views == 0 || (ortho_planes && pair_planes && n_pairs > 0 && n_planes > 0),
+               "rd_assemble_grid_tiles_aug: ortho inputs missing");
+    RD_REQUIRE(dsm_mode >= 0 && dsm_mode <= 2 && ortho_mode >= 0 && ortho_mode <= 2, "rd_assemble_grid_tiles_aug: bad mode");
+    (void)dsm_gt;       // accepted for the symmetry of the two signatures: nothing is cut from it
+    const long long plane = (long long)height * width;
+    const int S = tile / GRID_SLAB_ROWS;
+    const int want_dsm = dsm_mode == 2, want_ortho = ortho_mode == 2 && views > 0;
+    if (want_dsm || want_ortho)
+        RD_REQUIRE(ws && ws_bytes >= rd_assemble_grid_tiles_ws_bytes(n, tile),
+                   "rd_assemble_grid_tiles_aug: workspace too small (%zu < %zu bytes)", ws_bytes,
+                   rd_assemble_grid_tiles_ws_bytes(n, tile));
+    const double px = (double)n * tile * tile;
+    if (want_dsm || want_ortho) {
+        // the plain entry point's sums kernel with its arguments: the same partials, so the same means
+        const int aligned = (((uintptr_t)dsm_in | (uintptr_t)ortho_planes) % 16) == 0;
+        ProfScope ps((hipStream_t)s, "grid_tile_sums", 0, 4.0 * px * (want_dsm + (want_ortho ? views : 0)));
+        RD_LAUNCH(grid_tile_sums, dim3(n, S), dim3(256), 0, (hipStream_t)s, dsm_in, ortho_planes, (long)plane, height, width,
+                  n_planes, samples, pair_planes, n_pairs, views, tile, nodata, want_dsm, want_ortho, aligned, (double*)ws);
+        RD_LAUNCH_CHECK("grid_tile_sums");
+    }
+    const int planes_out = dsm_channel + views, cells = cdiv(tile, GRID_AUG_CELL);
+    ProfScope ps((hipStream_t)s, "grid_tile_write_aug", 0, px * 8.0 * planes_out);
+    RD_LAUNCH(grid_tile_write_aug, dim3(n, planes_out, cells * cells), dim3(256), 0, (hipStream_t)s, dsm_in, ortho_planes,
+              (long)plane, height, width, n_planes, samples, pair_planes, n_pairs, views, dsm_channel, tile, S, dsm_mode, dsm_mean,
+              dsm_std, ortho_mode, ortho_mean, ortho_std, (const double*)ws, aug, input, dsm_mean_out);
+    RD_LAUNCH_CHECK("grid_tile_write_aug");
     return RD_OK;
 }
 

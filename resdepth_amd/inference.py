@@ -316,9 +316,21 @@ def predict_linear_blend(dataloader, model, reduce_to_rank0: bool = True, host=N
                 pos = pos - lo_t
             if mean.numel() != n or pos.shape[0] != n:
                 raise ValueError("batch dict fields must hold one value per tile")
+            aug, log2_variants = None, 0
+            if "tta" in batch:
+                # test-time augmentation (GpuGridTiles(tta=...), or a host loader that supplies the same column and
+                # `dataset.tta`): sample i is oriented by code tta[i], and a tile's len(dataset.tta) variants follow each other
+                tta = getattr(ds, "tta", None)                # a tuple here, any sequence or array from a host dataset
+                variants = 0 if tta is None else len(tta)
+                if variants not in (1, 2, 4, 8, 16):
+                    raise ValueError("a batch with a 'tta' column needs dataset.tta = the 1, 2, 4, 8 or 16 variant codes of a tile")
+                log2_variants = variants.bit_length() - 1
+                aug = torch.as_tensor(batch["tta"]).flatten().to(device=device, dtype=torch.int32).contiguous()
+                if aug.numel() != n:
+                    raise ValueError("batch dict fields must hold one value per tile")
             with _lib.device_of(raster):
                 ops.blend_accumulate(y_pred.contiguous(), mean.contiguous(), std.contiguous(), pos.contiguous(),
-                                     reg.contiguous(), tile_size, stride, raster)
+                                     reg.contiguous(), tile_size, stride, raster, aug=aug, log2_variants=log2_variants)
                 done += n
                 if copier is not None and front is not None and done < len(front):
                     copier.advance(front[done])

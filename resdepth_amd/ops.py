@@ -743,12 +743,24 @@ def nhwc_to_nchw(x):
     return out
 
 
-def blend_accumulate(pred, mean, std, pos, reg, tile_size, stride, raster):
-    """raster (float64 [rows, cols], device) += blend-weighted de-normalised tiles; pos/reg int32 device tensors."""
+def blend_accumulate(pred, mean, std, pos, reg, tile_size, stride, raster, aug=None, log2_variants=0):
+    """raster (float64 [rows, cols], device) += blend-weighted de-normalised tiles; pos/reg int32 device tensors.
+    aug (int32 [n], device: the orientation code of every prediction, tiling.tta_codes) and log2_variants (0..4): test-time
+    augmentation -- every prediction is turned back into the raster's orientation and weighs 2^-log2_variants
+    (rd_blend_accumulate_tta); without them the call is rd_blend_accumulate."""
     n = pred.shape[0]
     rows, cols = raster.shape
     if raster.dtype != torch.float64 or pos.dtype != torch.int32 or reg.dtype != torch.int32:
         raise TypeError("blend_accumulate: raster must be float64, pos/reg int32")
-    check(load().rd_blend_accumulate(ptr(_f32(pred, "pred")), ptr(mean), ptr(std), ptr(pos), ptr(reg), n, tile_size,
-                                     stride, ptr(raster), rows, cols, stream_ptr()), "blend_accumulate")
+    if aug is None and int(log2_variants) == 0:
+        check(load().rd_blend_accumulate(ptr(_f32(pred, "pred")), ptr(mean), ptr(std), ptr(pos), ptr(reg), n, tile_size,
+                                         stride, ptr(raster), rows, cols, stream_ptr()), "blend_accumulate")
+        return raster
+    if aug is not None and (aug.dtype != torch.int32 or aug.numel() != n):
+        raise TypeError("blend_accumulate: aug must be int32 with one code per tile")
+    if tuple(pred.shape[-2:]) != (tile_size, tile_size):
+        raise ValueError("blend_accumulate: oriented predictions must be tile_size x tile_size")
+    check(load().rd_blend_accumulate_tta(ptr(_f32(pred, "pred")), ptr(mean), ptr(std), ptr(pos), ptr(reg), ptr(aug), n,
+                                         tile_size, stride, int(log2_variants), ptr(raster), rows, cols, stream_ptr()),
+          "blend_accumulate_tta")
     return raster

@@ -8,6 +8,8 @@ per-channel numpy loops and cannot feed more than a few hundred tiles/s.
 Raster I/O (GeoTIFF via GDAL) and the choice of valid patch positions stay with the caller (out of scope)."""
 from __future__ import annotations
 
+import warnings
+
 import torch
 
 from . import tiling
@@ -158,10 +160,14 @@ class GridTileSet:
     """`loader.dataset` of a GpuGridTiles: what predict_linear_blend and the Trainer read from a dataset (tile_size, stride,
     raster_shape, len(), `pos` in loader order, `shard` / `shard_plan`), plus the per-sample boxes and pair indices."""
 
-    def __init__(self, tile_size, stride, raster_shape, pos, reg, pair_idx, shard, shard_plan):
+    def __init__(self, tile_size, stride, raster_shape, pos, reg, pair_idx, shard, shard_plan, tta=None, tta_code=None,
+                 tta_swap=None):
         self.tile_size, self.stride, self.raster_shape = int(tile_size), int(stride), tuple(raster_shape)
         self.pos, self.reg, self.pair_idx = pos, reg, pair_idx
         self.shard, self.shard_plan = shard, shard_plan
+        # test-time augmentation (GpuGridTiles(tta=...)): `tta` = the variant codes -- every tile is len(tta) consecutive
+        # samples --, tta_code / tta_swap = orientation code and view-swap flag of every sample.  All None without it.
+        self.tta, self.tta_code, self.tta_swap = tta, tta_code, tta_swap
 
     def __len__(self):
         return len(self.pos)
@@ -179,12 +185,25 @@ class GpuGridTiles:
 
     dsm_mean: None (or 0.0, the reference's `if not self.dsm_mean`) = each tile's mean over its input pixels != nodata; a
     tile whose input is all nodata gets NaN (0 / 0, as GpuPatchSampler).  The ortho mean / std and the DSM std are the
-    sampler's.  shard=(rank, world): this rank's row band of a 'test' sweep (tiling.band_shards, as SyntheticRasterTiles)."""
+    sampler's.  shard=(rank, world): this rank's row band of a 'test' sweep (tiling.band_shards, as SyntheticRasterTiles).
+
+    tta / tta_swap_views (strategy 'test' only): test-time augmentation of the sweep.  tta = "none", "flips", "d4" or a sequence
+    of orientation codes (tiling.tta_codes: k | flip_v << 2 | flip_h << 3, the training loaders' transforms); tta_swap_views
+    doubles the variants by showing the pair's views in reverse order (the reference's permute_images_within_pair; needs two
+    or more views).  With a per-tile ortho mean (ortho_mean None) a swapped sample's mean is summed with the views in
+    reverse order: fp64 sums of fp32 pixels, exact -- and so the plain tile's mean whatever the order -- as long as every non-zero
+    pixel is at least 2^-29 of the tile's sum in magnitude (its last fp32 bit is then no finer than the sum's fp64 ulp); below
+    that the two orders may differ by roundings of the fp64 sum, far under the fp32 rounding of the mean.  The sample list is this rank's plain list with every tile repeated once per variant, tile-major and
+    variant-minor; `dataset` (pos, reg, pair_idx, len(), plus tta / tta_code / tta_swap) describes that list.  Batches carry the
+    int32 device column "tta" (the orientation code of every sample), `input` in that orientation with the PLAIN tile's
+    dsm_mean, and NO target / loss_mask: the variants are for prediction.  predict_linear_blend turns every prediction back
+    and averages a tile's variants with the exact weight 1 / variants (rd_blend_accumulate_tta); the sweep costs variants x
+    tiles forwards.  tta=None and tta_swap_views=False: the loader is what it was (rd_assemble_grid_tiles, no "tta" column)."""
 
     def __init__(self, sampler: GpuPatchSampler, strategy: str, area_defn, input_channels: str = "geom-stereo",
                  image_pairs=None, stride=None, dsm_mean=None, transform_dsm: bool = True, transform_orthos: bool = True,
                  batch_size: int = 32, shard=(0, 1), prefetch: int = 1, augment: bool = False,
-                 permute_images_within_pair: bool = False):
+                 permute_images_within_pair: bool = False, tta=None, tta_swap_views: bool = False):
         if augment:
             raise ValueError("GpuGridTiles: augment=True is not supported (the reference augments 'train' samples only)")
         if permute_images_within_pair:
@@ -232,7 +251,26 @@ class GpuGridTiles:
         if not 0 < stride <= t:
             raise ValueError(f"GpuGridTiles: stride must be in 1..{t} (got {stride})")
         pos, reg, pair_idx, plan = tiling.grid_shard(strategy, pos, reg, pair_idx, t, sampler.h, (rank, world))
-        self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan)
+        self.tta = tta is not None or bool(tta_swap_views)
+        if self.tta:
+            if strategy != "test":
+                raise ValueError("GpuGridTiles: tta is for strategy='test' (prediction); validation tiles keep one orientation")
+            codes = tiling.tta_codes(tta, bool(tta_swap_views))
+            if tta_swap_views and self.views < 2:
+                raise ValueError("GpuGridTiles: tta_swap_views needs an image pair of two or more views")
+            if sampler.dsm_gt is not None:
+                warnings.warn("GpuGridTiles: with tta the batches carry no target / loss_mask (the sampler's ground truth is "
+                              "not read); use a loader without tta where a loss or a per-tile metric is needed", stacklevel=2)
+            pos, reg, pair_idx, code, swap, variants = tiling.tta_expand(pos, reg, pair_idx, codes, bool(tta_swap_views))
+            rows6 = pair_idx
+            if tta_swap_views:      # rows n_pairs .. 2 n_pairs - 1 of the pair -> plane table: the pairs with their views reversed
+                rows6 = [p + len(pairs) * sw for p, sw in zip(pair_idx, swap)]
+                pairs = pairs + [pr[::-1] for pr in pairs]
+            self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan, variants,
+                                       code, swap)
+        else:
+            rows6 = pair_idx
+            self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan)
         # transform modes of rd_assemble_grid_tiles: 0 raw, 1 the given mean, 2 the tile's mean (`not mean`: the reference's test)
         self.dsm_mode = 0 if not transform_dsm else (2 if not dsm_mean else 1)
         self.dsm_mean = float(dsm_mean) if self.dsm_mode == 1 else 0.0
@@ -245,10 +283,11 @@ class GpuGridTiles:
         if n:
             tab[:n, 0:2] = torch.tensor(pos, dtype=torch.int32)
             tab[:n, 2:6] = torch.tensor(reg, dtype=torch.int32)
-            tab[:n, 6] = torch.tensor(pair_idx, dtype=torch.int32)
+            tab[:n, 6] = torch.tensor(rows6, dtype=torch.int32)
         # uploaded once per loader: the kernels' sample table, the pair -> plane table and the int64 metadata columns
         self._table = tab.to(dev)
         self._pair_planes = torch.tensor(pairs, dtype=torch.int32).to(dev) if views else None
+        self._aug = torch.tensor(self.dataset.tta_code, dtype=torch.int32).reshape(-1).to(dev) if self.tta else None
         self._meta = {k: tab[:n, c].to(torch.int64).to(dev) for c, k in enumerate(
             ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
              "patch_valid_pixels_lrx"))}
@@ -271,21 +310,25 @@ class GpuGridTiles:
         inp = torch.empty(n, c, t, t, dtype=torch.float32, device=dev)
         mean = torch.empty(n, dtype=torch.float32, device=dev)
         tgt = msk = None
-        if src.dsm_gt is not None:
+        if src.dsm_gt is not None and not self.tta:      # oriented samples are for prediction: no target / loss_mask
             tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
             msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
         lib = load()
         need = lib.rd_assemble_grid_tiles_ws_bytes(n, t)
         if ws is None or ws.numel() < need:
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        check(lib.rd_assemble_grid_tiles(
-            ptr(src.dsm_in), ptr(src.dsm_gt), ptr(src.orthos) if v else None, src.orthos.shape[0] if v else 0, src.h, src.w,
-            self._table.data_ptr() + k0 * 8 * 4, ptr(self._pair_planes) if v else None,
-            self._pair_planes.shape[0] if v else 0, v, self.dsm_channel, n, t, src.nodata, self.dsm_mode, self.dsm_mean,
-            src.dsm_std, self.ortho_mode, self.ortho_mean, src.ortho_std, ptr(inp), ptr(tgt), ptr(msk), ptr(mean), ptr(ws),
-            ws.numel(), stream_ptr()), "assemble_grid_tiles")
+        head = (ptr(src.dsm_in), ptr(src.dsm_gt) if tgt is not None else None, ptr(src.orthos) if v else None,
+                src.orthos.shape[0] if v else 0, src.h, src.w, self._table.data_ptr() + k0 * 8 * 4,
+                ptr(self._pair_planes) if v else None, self._pair_planes.shape[0] if v else 0, v, self.dsm_channel, n, t,
+                src.nodata, self.dsm_mode, self.dsm_mean, src.dsm_std, self.ortho_mode, self.ortho_mean, src.ortho_std)
+        tail = (ptr(inp), ptr(tgt), ptr(msk), ptr(mean), ptr(ws), ws.numel(), stream_ptr())
         batch = {"input": inp, "dsm_mean": mean, "dsm_std": torch.full((n,), src.dsm_std, device=dev),
                  "nodata": torch.full((n,), src.nodata, device=dev)}
+        if self.tta:        # the same arguments plus the orientation code of every sample
+            batch["tta"] = self._aug[k0:k1]
+            check(lib.rd_assemble_grid_tiles_aug(*head, ptr(batch["tta"]), *tail), "assemble_grid_tiles_aug")
+        else:
+            check(lib.rd_assemble_grid_tiles(*head, *tail), "assemble_grid_tiles")
         for key, col in self._meta.items():
             batch[key] = col[k0:k1]
         if tgt is not None:

@@ -168,6 +168,75 @@ def grid_shard(strategy: str, pos, reg, pair_idx, tile_size: int, rows: int, sha
     return list(pos[i0:i1]), list(reg[i0:i1]), list(pair_idx[i0:i1]), plan
 
 
+# ---- test-time augmentation: variants of a tile under the square's symmetry group ----------------------------------------
+# A code is the training loaders' aug = k | flip_v << 2 | flip_h << 3: rot90(k) -> flipud -> fliplr (lib/torch_transforms.py).
+TTA_SETS = {"none": (0,), "flips": (0, 4, 8, 12), "d4": tuple(k | (h << 3) for k in range(4) for h in (0, 1))}
+
+
+def tta_codes(spec, swap_views: bool = False):
+    """Variant codes of a test-time-augmentation set -> tuple of ints in 0..15.  spec: None / "none" = (0,); "flips" = identity,
+    flipud, fliplr, both; "d4" = the eight elements of the square's symmetry group (k = 0..3, each without and with fliplr, in
+    that order); or an explicit sequence of codes.  The number of variants (doubled by `swap_views`) must be 1, 2, 4, 8 or 16:
+    the blend weighs every variant by 1 / variants, which is exact -- and commutes with every rounding -- for powers of two only."""
+    if spec is None:
+        codes = TTA_SETS["none"]
+    elif isinstance(spec, str):
+        if spec not in TTA_SETS:
+            raise ValueError(f"tta must be one of {sorted(TTA_SETS)} or a sequence of codes (got {spec!r})")
+        codes = TTA_SETS[spec]
+    else:
+        try:
+            codes = tuple(spec)
+        except TypeError:
+            raise ValueError(f"tta must be one of {sorted(TTA_SETS)} or a sequence of codes (got {spec!r})") from None
+        for c in codes:
+            if isinstance(c, bool) or int(c) != c or not 0 <= int(c) <= 15:
+                raise ValueError(f"tta codes are integers in 0..15 (k | flip_v << 2 | flip_h << 3), got {c!r}")
+        codes = tuple(int(c) for c in codes)
+    n = len(codes) * (2 if swap_views else 1)
+    if n not in (1, 2, 4, 8, 16):
+        raise ValueError(f"the number of tta variants must be 1, 2, 4, 8 or 16 (got {n})")
+    return codes
+
+
+def tta_apply(x, code: int):
+    """The oriented form of a numpy array [..., T, T] under `code`: rot90(k) -> flipud -> fliplr on the last two axes."""
+    import numpy as np
+    code = int(code)
+    y = np.rot90(x, code & 3, axes=(-2, -1))
+    if code & 4:
+        y = np.flip(y, -2)
+    if code & 8:
+        y = np.flip(y, -1)
+    return np.ascontiguousarray(y)
+
+
+def tta_undo(y, code: int):
+    """Inverse of `tta_apply`: fliplr -> flipud -> rot90(-k)."""
+    import numpy as np
+    code = int(code)
+    x = y
+    if code & 8:
+        x = np.flip(x, -1)
+    if code & 4:
+        x = np.flip(x, -2)
+    return np.ascontiguousarray(np.rot90(x, -(code & 3), axes=(-2, -1)))
+
+
+def tta_expand(pos, reg, pair_idx, codes, swap_views: bool = False):
+    """A sample list with every tile repeated once per variant, tile-major and variant-minor -> (pos, reg, pair_idx, code per
+    sample, view-swap flag per sample, the variant codes).  The variants are `codes`, then (swap_views) `codes` again with the
+    pair's views in reverse order.  Applied AFTER grid_shard: a tile's variants stay on the tile's rank and next to each other,
+    so the band plan, the frontier bookkeeping of predict_linear_blend and the per-pixel blend order see G samples where they
+    saw one."""
+    variants = [(c, 0) for c in codes] + ([(c, 1) for c in codes] if swap_views else [])
+    g = len(variants)
+    rep = lambda xs: [x for x in xs for _ in range(g)]
+    n = len(pos)
+    return (rep(pos), rep(reg), rep(pair_idx), [c for c, _ in variants] * n, [s for _, s in variants] * n,
+            tuple(c for c, _ in variants))
+
+
 # ---- the training set: sampling_strategy 'train' of the reference's `_determine_patches` (lib/DsmOrthoDataset.py:316-371) ----
 def _train_regions(area_defn, tile_size: int):
     """[(y_start, x_start, n_y, n_x)] per region of `area_defn`: the valid upper-left positions of

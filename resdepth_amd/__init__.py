@@ -11,6 +11,7 @@ from .graph import GraphedTrainStep  # noqa: F401
 from .plan import PlannedTrainStep  # noqa: F401
 from .data import SyntheticDsmOrthoDataset, synthetic_batch  # noqa: F401
 from .inference import predict_linear_blend, SyntheticRasterTiles  # noqa: F401
+from .ensemble import PairSweep, predict_pairs_linear_blend  # noqa: F401
 from .sampler import GpuGridTiles, GpuPatchSampler, GpuTrainSet, GpuValSet, SamplerLoader  # noqa: F401
 from . import normalization  # noqa: F401
 from .evaluation import (dilate_mask, evaluate_performance, evaluate_statistics, get_statistics_masked,  # noqa: F401
@@ -19,6 +20,6 @@ from .factories import (get_loss, get_model, get_scheduler, get_trainer, valid_t
                         validate_tile_size)
 
 __all__ = ["UNet", "SkipConnection", "MaskedL1Loss", "masked_l1_loss", "FusedAdam", "FusedSGD", "get_optimizer", "Trainer", "AverageMeter", "DevicePrefetcher", "GraphedTrainStep", "PlannedTrainStep",
-           "SyntheticDsmOrthoDataset", "synthetic_batch", "predict_linear_blend", "SyntheticRasterTiles",
+           "SyntheticDsmOrthoDataset", "synthetic_batch", "predict_linear_blend", "SyntheticRasterTiles", "predict_pairs_linear_blend", "PairSweep",
            "GpuPatchSampler", "SamplerLoader", "GpuGridTiles", "GpuTrainSet", "GpuValSet", "normalization", "get_loss", "get_model", "get_scheduler", "get_trainer", "valid_tile_size", "validate_tile_size",
            "dilate_mask", "evaluate_statistics", "evaluate_performance", "print_statistics", "get_statistics_masked"]

@@ -163,6 +163,11 @@ SIGNATURES_TTA = {
     "rd_blend_accumulate_tta": (I, [P, P, P, P, P, P, I, I, I, I, P, I, I, P]),
     "rd_assemble_grid_tiles_aug": (I, [P, P, P, I, I, I, P, P, I, I, I, I, I, F, I, F, F, I, F, F, P, P, P, P, P, P, SZ, P]),
 }
+# include/resdepth_hip_pairs.h (all image pairs in one sweep), one to one as above; to be folded into SIGNATURES with that header
+SIGNATURES_PAIRS = {
+    "rd_blend_accumulate_planes": (I, [P, P, P, P, P, P, P, I, I, I, I, P, I, LL, I, I, P]),
+    "rd_fuse_planes": (I, [P, LL, I, LL, I, P, I, P, P]),
+}
 
 
 class ProfEntry(C.Structure):
@@ -183,7 +188,7 @@ def load():
                 f"resdepth_amd: HIP library not built ({LIB_PATH} missing). Run resdepth_amd/csrc/build.sh; "
                 "there is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

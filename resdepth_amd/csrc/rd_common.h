@@ -303,6 +303,23 @@ __device__ __forceinline__ void st_nt1(float* p, float v) {
     __builtin_nontemporal_store(v, p);
 #endif
 }
+// fp64 rasters read once (rd_fuse_planes): one double, or two as ONE 16-byte access (p 16-byte aligned)
+typedef double rd_f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ double ld_nt_f64(const double* p) {
+#ifdef RD_NO_NT
+    return *p;
+#else
+    return __builtin_nontemporal_load(p);
+#endif
+}
+__device__ __forceinline__ double2 ld_nt_f64x2(const double* p) {
+#ifdef RD_NO_NT
+    return *reinterpret_cast<const double2*>(p);
+#else
+    const rd_f64x2 v = __builtin_nontemporal_load(reinterpret_cast<const rd_f64x2*>(p));
+    return make_double2(v.x, v.y);
+#endif
+}
 __device__ __forceinline__ uchar4 ld_nt_u8x4(const unsigned char* p) {
 #ifdef RD_NO_NT
     return *reinterpret_cast<const uchar4*>(p);

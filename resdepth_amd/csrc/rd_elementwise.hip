@@ -1101,13 +1101,26 @@ __device__ __forceinline__ double blend_tta_add(double acc, float den, double w,
     return fma((double)den * scale, w, acc);
 }
 
+//
+// PLANES (rd_blend_accumulate_planes): sample i goes into raster + plane[i] * plane_stride, one of n_planes rasters of
+// rows x cols.  Samples of different planes never meet: sample j < i takes a pixel from sample i only if plane[j] == plane[i],
+// and an owner adds only the samples of its own plane -- so every plane sees its own samples in their order, as if the others
+// were not in the call.  A plane index outside 0 .. n_planes - 1 owns nothing and equals no valid plane: the sample is skipped.
+// Without PLANES the kernel is rd_blend_accumulate_tta's, instruction for instruction.
+template <bool PLANES>
 __global__ __launch_bounds__(256) void blend_tta_kernel(const float* __restrict__ pred, const float* __restrict__ mean,
                                                         const float* __restrict__ stdv, const int* __restrict__ pos,
-                                                        const int* __restrict__ reg, const int* __restrict__ aug, int first,
-                                                        int last, int T, int stride, double scale,
-                                                        double* __restrict__ raster, int rows, int cols) {
+                                                        const int* __restrict__ reg, const int* __restrict__ aug,
+                                                        const int* __restrict__ plane, int first, int last, int T, int stride,
+                                                        double scale, double* __restrict__ raster, int n_planes,
+                                                        long plane_stride, int rows, int cols) {
     __shared__ float stage[TTA_CELL * (TTA_CELL + 1)];
     const int i = first + blockIdx.y, t = threadIdx.x;
+    const int pl = PLANES && plane ? plane[i] : 0;
+    if (PLANES) {
+        if ((unsigned)pl >= (unsigned)n_planes) return;    // uniform over the block, before any barrier
+        raster += (long)pl * plane_stride;
+    }
     const int cells = (T + TTA_CELL - 1) / TTA_CELL;
     const int R0 = (blockIdx.x / cells) * TTA_CELL, C0 = (blockIdx.x % cells) * TTA_CELL;
     const int Y0 = pos[i * 2] + R0, X0 = pos[i * 2 + 1] + C0;                       // the cell's raster rectangle
@@ -1121,7 +1134,9 @@ __global__ __launch_bounds__(256) void blend_tta_kernel(const float* __restrict_
         const int y = Y0 + lr + 8 * q;
         own[q] = lc < w && lr + 8 * q < h && (unsigned)y < (unsigned)rows && (unsigned)x < (unsigned)cols;
         for (int j = first; own[q] && j < i; ++j)
-            if ((unsigned)(y - pos[j * 2]) < (unsigned)T && (unsigned)(x - pos[j * 2 + 1]) < (unsigned)T) own[q] = false;
+            if ((unsigned)(y - pos[j * 2]) < (unsigned)T && (unsigned)(x - pos[j * 2 + 1]) < (unsigned)T &&
+                (!PLANES || !plane || plane[j] == pl))
+                own[q] = false;
         acc[q] = own[q] ? raster[(long)y * cols + x] : 0.0;
         any = any || own[q];
     }
@@ -1129,6 +1144,7 @@ __global__ __launch_bounds__(256) void blend_tta_kernel(const float* __restrict_
     const int overlap = T - stride;
     const double step = overlap > 1 ? 1.0 / (double)(overlap - 1) : 0.0;
     for (int j = i; j < last; ++j) {
+        if (PLANES && plane && plane[j] != pl) continue;   // another plane's sample: uniform over the block
         const int yj = pos[j * 2], xj = pos[j * 2 + 1];
         // the cell's part of tile j, in tile j's plain coordinates [a0, a1) x [b0, b1): uniform over the block
         const int a0 = max(Y0 - yj, 0), a1 = min(Y0 + h - yj, T), b0 = max(X0 - xj, 0), b1 = min(X0 + w - xj, T);
@@ -2303,10 +2319,34 @@ int rd_blend_accumulate_tta(const float* pred, const float* mean, const float* s
     // launch adds after an earlier one -- rd_blend_accumulate's per-pixel order for any n
     for (int first = 0; first < n; first += 64) {
         const int last = first + 64 < n ? first + 64 : n;
-        RD_LAUNCH(blend_tta_kernel, dim3(cells * cells, last - first), dim3(256), 0, (hipStream_t)s, pred, mean, stdv, pos, reg,
-                  aug, first, last, tile_size, stride, scale, raster, rows, cols);
+        RD_LAUNCH(blend_tta_kernel<false>, dim3(cells * cells, last - first), dim3(256), 0, (hipStream_t)s, pred, mean, stdv, pos,
+                  reg, aug, nullptr, first, last, tile_size, stride, scale, raster, 1, 0L, rows, cols);
     }
     RD_LAUNCH_CHECK("blend_accumulate_tta");
+    return RD_OK;
+}
+
+int rd_blend_accumulate_planes(const float* pred, const float* mean, const float* stdv, const int* pos, const int* reg,
+                               const int* aug, const int* plane, int n, int tile_size, int stride, int log2_variants,
+                               double* raster, int n_planes, long long plane_stride, int rows, int cols, rd_stream_t s) {
+    RD_REQUIRE(pred && mean && stdv && pos && reg && raster, "rd_blend_accumulate_planes: null pointer");
+    RD_REQUIRE(n > 0 && tile_size > 0 && stride > 0 && stride <= tile_size && rows > 0 && cols > 0,
+               "rd_blend_accumulate_planes: bad shape (n=%d tile=%d stride=%d raster=%dx%d)", n, tile_size, stride, rows, cols);
+    RD_REQUIRE(log2_variants >= 0 && log2_variants <= 4, "rd_blend_accumulate_planes: log2_variants must be in 0..4 (got %d)",
+               log2_variants);
+    RD_REQUIRE(n_planes >= 1 && plane_stride >= (long long)rows * cols,
+               "rd_blend_accumulate_planes: n_planes must be positive and plane_stride >= rows x cols (n_planes=%d "
+               "plane_stride=%lld raster=%dx%d)", n_planes, plane_stride, rows, cols);
+    ProfScope ps((hipStream_t)s, "blend_accumulate_planes", 0, 20.0 * n * tile_size * tile_size);
+    const int cells = cdiv(tile_size, TTA_CELL);
+    const double scale = 1.0 / (double)(1 << log2_variants);
+    // rd_blend_accumulate_tta's launches: up to 64 samples each, in order
+    for (int first = 0; first < n; first += 64) {
+        const int last = first + 64 < n ? first + 64 : n;
+        RD_LAUNCH(blend_tta_kernel<true>, dim3(cells * cells, last - first), dim3(256), 0, (hipStream_t)s, pred, mean, stdv, pos,
+                  reg, aug, plane, first, last, tile_size, stride, scale, raster, n_planes, (long)plane_stride, rows, cols);
+    }
+    RD_LAUNCH_CHECK("blend_accumulate_planes");
     return RD_OK;
 }
 

@@ -650,3 +650,178 @@ int rd_residual_stats_sets(const double* src0, const double* src1, const uint8_t
 }
 
 }  // extern "C"
+
+// ---- per-pixel fusion of P rasters of one surface (rd_fuse_planes, include/resdepth_hip_pairs.h) -----------------------
+// A streaming kernel: P x 8 bytes in, 8 or 16 out per pixel.  A thread takes TWO neighbouring pixels, so every plane is read
+// with one 16-byte non-temporal load per thread (8-byte accesses reach 0.54-0.70 of the 16-byte rate on this part) and the
+// outputs leave as 16-byte stores; the P loads of a thread are independent and in flight together.  The 2 x P values live
+// in registers: the kernel is a template on P and every index below is a compile-time constant -- the sorting network is a
+// constexpr table applied through an index sequence, because an array indexed by a runtime value goes to scratch
+// (scripts/check_isa.sh fails the build on any).  The modes are wave-uniform branches.
+// Order rules (the header states them; a float64 host loop reproduces mean / median / range bit for bit):
+//   mean    acc = v_0; acc = acc + v_p (p = 1 .. P - 1); acc / P            (a division, not a multiply by 1 / P)
+//   median  ascending order statistics; odd P: the middle one; even P: (a + b) * 0.5 of the two middle ones (np.median)
+//   range   max - min                  std  sqrt(sum_p (v_p - mean)^2 / P), summed in plane order
+//   a NaN in any plane -> NaN in every output of the pixel (min / max / the network alone would drop it)
+namespace rd {
+
+constexpr int FUSE_MAX_P = 16;
+constexpr int FUSE_MAX_CE = 63;         // Batcher's odd-even merge sort: 63 comparators at n = 16, fewer below
+
+struct SortNet {
+    int n;
+    int a[FUSE_MAX_CE], b[FUSE_MAX_CE];
+};
+
+// Batcher's odd-even merge sort for ANY n (the partner test `/ (2 p)` keeps a comparator inside its merge block, which is
+// what makes the n < 2^k networks the 2^k network with the comparators that touch a missing wire dropped)
+constexpr SortNet make_sort_net(int n) {
+    SortNet net{};
+    for (int p = 1; p < n; p *= 2)
+        for (int k = p; k >= 1; k /= 2)
+            for (int j = k % p; j + k < n; j += 2 * k)
+                for (int i = 0; i < k && i + j + k < n; ++i)
+                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
+                        net.a[net.n] = i + j;
+                        net.b[net.n] = i + j + k;
+                        ++net.n;
+                    }
+    return net;
+}
+
+__device__ __forceinline__ void fuse_cmpswap(double& lo, double& hi) {
+    const double x = lo, y = hi;
+    const bool sw = y < x;              // a NaN never swaps; the pixel's outputs are overwritten with NaN anyway
+    lo = sw ? y : x;
+    hi = sw ? x : y;
+}
+
+template <int P, size_t... I>
+__device__ __forceinline__ void fuse_sort(double (&v)[P], std::index_sequence<I...>) {
+    constexpr SortNet net = make_sort_net(P);
+    (fuse_cmpswap(v[net.a[I]], v[net.b[I]]), ...);
+}
+
+// one pixel: v[] = its P values in plane order (sorted in place when the median is asked for)
+template <int P>
+__device__ __forceinline__ void fuse_pixel(double (&v)[P], int fuse_mode, int spread_mode, double& fused, double& spread) {
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    bool nan = false;
+    double acc = v[0];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        nan = nan || v[p] != v[p];
+        if (p) acc = acc + v[p];
+    }
+    const double mean = acc / (double)P;
+    spread = 0.0;
+    if (spread_mode == RD_SPREAD_RANGE) {
+        double lo = v[0], hi = v[0];
+#pragma unroll
+        for (int p = 1; p < P; ++p) {
+            lo = v[p] < lo ? v[p] : lo;
+            hi = v[p] > hi ? v[p] : hi;
+        }
+        spread = hi - lo;
+    } else if (spread_mode == RD_SPREAD_STD) {
+        double ss = 0.0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const double d = v[p] - mean;
+            ss = ss + d * d;
+        }
+        spread = sqrt(ss / (double)P);
+    }
+    fused = mean;
+    if (fuse_mode == RD_FUSE_MEDIAN) {
+        constexpr int n_ce = make_sort_net(P).n;
+        fuse_sort<P>(v, std::make_index_sequence<n_ce>{});
+        fused = (P & 1) ? v[P / 2] : (v[(P - 1) / 2] + v[P / 2]) * 0.5;
+    }
+    if (nan) fused = spread = nanv;
+}
+
+template <int P, bool VEC>
+__global__ __launch_bounds__(256) void fuse_planes_kernel(const double* __restrict__ planes, long plane_stride, long n,
+                                                          int fuse_mode, int spread_mode, double* __restrict__ fused,
+                                                          double* __restrict__ spread) {
+    const long t0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+    long tail = 0;                      // first pixel of the scalar part
+    if (VEC) {
+        // planes, plane_stride, fused and spread allow 16-byte accesses (the launcher checked): pixel pairs (2 q, 2 q + 1)
+        const long pairs = n >> 1;
+        for (long q = t0; q < pairs; q += step) {
+            double a[P], b[P];
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const double2 d = ld_nt_f64x2(planes + (long)p * plane_stride + 2 * q);
+                a[p] = d.x;
+                b[p] = d.y;
+            }
+            double fa, sa, fb, sb;
+            fuse_pixel<P>(a, fuse_mode, spread_mode, fa, sa);
+            fuse_pixel<P>(b, fuse_mode, spread_mode, fb, sb);
+            *reinterpret_cast<double2*>(fused + 2 * q) = make_double2(fa, fb);
+            if (spread_mode != RD_SPREAD_NONE) *reinterpret_cast<double2*>(spread + 2 * q) = make_double2(sa, sb);
+        }
+        tail = pairs * 2;               // an odd n leaves one pixel
+    }
+    for (long i = tail + t0; i < n; i += step) {
+        double a[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) a[p] = ld_nt_f64(planes + (long)p * plane_stride + i);
+        double fa, sa;
+        fuse_pixel<P>(a, fuse_mode, spread_mode, fa, sa);
+        fused[i] = fa;
+        if (spread_mode != RD_SPREAD_NONE) spread[i] = sa;
+    }
+}
+
+template <int P>
+static void fuse_launch(bool vec, int grid, hipStream_t s, const double* planes, long plane_stride, long n, int fuse_mode,
+                        int spread_mode, double* fused, double* spread) {
+    if (vec)
+        RD_LAUNCH((fuse_planes_kernel<P, true>), dim3(grid), dim3(256), 0, s, planes, plane_stride, n, fuse_mode, spread_mode,
+                  fused, spread);
+    else
+        RD_LAUNCH((fuse_planes_kernel<P, false>), dim3(grid), dim3(256), 0, s, planes, plane_stride, n, fuse_mode, spread_mode,
+                  fused, spread);
+}
+
+}  // namespace rd
+
+extern "C" {
+
+int rd_fuse_planes(const double* planes, long long plane_stride, int n_planes, long long n, int fuse_mode, double* fused,
+                   int spread_mode, double* spread, rd_stream_t s_) {
+    RD_REQUIRE(planes && fused, "rd_fuse_planes: null pointer");
+    RD_REQUIRE(n_planes >= 1 && n_planes <= FUSE_MAX_P, "rd_fuse_planes: n_planes must be in 1..%d (got %d)", FUSE_MAX_P,
+               n_planes);
+    RD_REQUIRE(n > 0 && plane_stride >= n, "rd_fuse_planes: bad shape (n=%lld plane_stride=%lld)", n, plane_stride);
+    RD_REQUIRE(fuse_mode == RD_FUSE_MEAN || fuse_mode == RD_FUSE_MEDIAN, "rd_fuse_planes: unknown fuse_mode %d", fuse_mode);
+    RD_REQUIRE(spread_mode == RD_SPREAD_NONE || spread_mode == RD_SPREAD_RANGE || spread_mode == RD_SPREAD_STD,
+               "rd_fuse_planes: unknown spread_mode %d", spread_mode);
+    RD_REQUIRE(spread_mode == RD_SPREAD_NONE || spread, "rd_fuse_planes: spread_mode %d needs the spread output", spread_mode);
+    hipStream_t s = (hipStream_t)s_;
+    const bool want_spread = spread_mode != RD_SPREAD_NONE;
+    // 16-byte accesses need every plane's base, the outputs and so the plane stride on 16-byte boundaries
+    const bool vec = (((uintptr_t)planes | (uintptr_t)fused | (want_spread ? (uintptr_t)spread : 0)) % 16) == 0 &&
+                     (n_planes == 1 || plane_stride % 2 == 0);
+    const long work = vec ? (long)((n + 1) / 2) : (long)n;
+    const int grid = stats_grid(work);
+    ProfScope ps(s, "fuse_planes", 0, 8.0 * n * (n_planes + 1 + (want_spread ? 1 : 0)));
+    switch (n_planes) {
+#define RD_FUSE_CASE(P_)                                                                                            \
+    case P_:                                                                                                        \
+        fuse_launch<P_>(vec, grid, s, planes, (long)plane_stride, (long)n, fuse_mode, spread_mode, fused, spread); \
+        break;
+        RD_FUSE_CASE(1) RD_FUSE_CASE(2) RD_FUSE_CASE(3) RD_FUSE_CASE(4) RD_FUSE_CASE(5) RD_FUSE_CASE(6) RD_FUSE_CASE(7)
+        RD_FUSE_CASE(8) RD_FUSE_CASE(9) RD_FUSE_CASE(10) RD_FUSE_CASE(11) RD_FUSE_CASE(12) RD_FUSE_CASE(13)
+        RD_FUSE_CASE(14) RD_FUSE_CASE(15) RD_FUSE_CASE(16)
+#undef RD_FUSE_CASE
+    }
+    RD_LAUNCH_CHECK("fuse_planes");
+    return RD_OK;
+}
+
+}  // extern "C"

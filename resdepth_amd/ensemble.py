@@ -1,0 +1,130 @@
+"""All image pairs of a raster in ONE tiled sweep, fused per pixel on the GPU.
+
+The reference predicts a raster once per image pair (test.py:136-189: a loader and a `predict_linear_blend` per entry of
+`dataset.image_pairs`) and pools the residuals of all pairs afterwards (test.py:288-313).  Here a
+GpuGridTiles(..., 'test', image_pairs=[P pairs], sweep_pairs=True) repeats every tile once per pair, tile-major and pair-minor,
+and `predict_pairs_linear_blend` blends the prediction of pair p into plane p of a [P, rows, cols] device raster
+(rd_blend_accumulate_planes), reduces the planes per pixel on the device (rd_fuse_planes: mean or median, and the range or
+standard deviation over the pairs) and brings back the fused surface, the spread and -- if asked -- the P planes.
+
+Eval-mode inference keeps one magnitude slot per image, so a tile's prediction depends on that tile alone, and the blend adds
+per pixel in sample order within a plane: plane p equals, bit for bit, today's single-pair sweep of pair p, whatever the batch
+size and wherever a batch cuts a tile's P samples."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .inference import _raster_shape
+from .trainer import DevicePrefetcher
+
+_META = ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
+         "patch_valid_pixels_lrx")
+
+
+class PairSweep:
+    """What predict_pairs_linear_blend returns: `fused` np.float64 [rows, cols]; `spread` [rows, cols] or None; `pairs`
+    np.float64 [P, rows, cols] (plane p = the sweep of image_pairs[p]) or None; `image_pairs`.  The arrays are views of pinned
+    host memory the object keeps alive (`host`: with host="reuse" the next call of the same shape overwrites them)."""
+
+    def __init__(self, fused, spread, pairs, image_pairs, host):
+        self.fused, self.spread, self.pairs, self.image_pairs, self.host = fused, spread, pairs, image_pairs, host
+
+
+class _PairHost:
+    """Pinned host memory of one call: P + 2 planes of rows x cols doubles at most (fused, spread, the P planes)."""
+
+    def __init__(self, planes, rows, cols):
+        self.key = (int(planes), int(rows), int(cols))
+        self.t = torch.empty(self.key, dtype=torch.float64, pin_memory=True)
+
+
+_host_cache = {}
+
+
+def predict_pairs_linear_blend(dataloader, model, fuse: str = "median", spread=None, return_pairs: bool = True, host=None):
+    """One sweep over a loader that carries the "pair" column (GpuGridTiles(..., sweep_pairs=True)) -> PairSweep.
+    fuse: "mean" | "median"; spread: None | "range" | "std" (ops.fuse_planes); return_pairs=False leaves the P planes on the
+    device and returns only the fused surface (and the spread): 8 or 16 bytes per raster pixel cross to the host instead of
+    8 (P + 1) or 8 (P + 2).  host: None = fresh pinned arrays per call; "reuse" = one cached block per (planes, rows, cols)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("resdepth_amd.predict_pairs_linear_blend runs on a HIP device only (no CPU fallback)")
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise RuntimeError("predict_pairs_linear_blend: a process group of world > 1 is not supported (the banded multi-GPU "
+                           "delivery holds one plane); sweep in one process")
+    if fuse not in ops.FUSE_MODES:
+        raise ValueError(f"predict_pairs_linear_blend: fuse must be one of {sorted(ops.FUSE_MODES)} (got {fuse!r})")
+    if spread not in ops.SPREAD_MODES:
+        raise ValueError(f"predict_pairs_linear_blend: spread must be None, 'range' or 'std' (got {spread!r})")
+    ds = dataloader.dataset
+    n_pairs = getattr(ds, "n_pairs", None)
+    if not n_pairs:
+        raise ValueError("predict_pairs_linear_blend needs a loader that sweeps its image pairs: dataset.n_pairs and the "
+                         "'pair' batch column (GpuGridTiles(..., image_pairs=[...], sweep_pairs=True))")
+    n_pairs = int(n_pairs)
+    first = next(model.parameters(), None)
+    device = first.device if first is not None and first.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    model.eval()
+    model.to(device)
+    rows, cols = _raster_shape(ds)
+    tile_size, stride = int(ds.tile_size), int(ds.stride)
+    raster = torch.zeros(n_pairs, rows, cols, dtype=torch.float64, device=device)
+    with torch.no_grad():
+        for batch in DevicePrefetcher(dataloader, device, 1):
+            if "pair" not in batch:
+                raise ValueError("predict_pairs_linear_blend: the batch has no 'pair' column (GpuGridTiles(..., sweep_pairs=True))")
+            x = batch["input"].to(device, non_blocking=True)
+            n = x.shape[0]
+            y_pred = model(x)
+            mean = torch.as_tensor(batch["dsm_mean"]).flatten().to(torch.float32).to(device)
+            std = torch.as_tensor(batch["dsm_std"]).flatten().to(torch.float32).to(device)
+            # the metadata block of predict_linear_blend: device columns as they are, host columns as one pinned int32 block
+            cols6 = [torch.as_tensor(batch[k]).flatten() for k in _META]
+            if any(c.is_cuda for c in cols6):
+                cols6 = [c.to(device) for c in cols6]
+                pos = torch.stack(cols6[0:2], 1).to(torch.int32)
+                reg = torch.stack(cols6[2:6], 1).to(torch.int32)
+            else:
+                blk = torch.cat([torch.stack(cols6[0:2], 1).flatten(), torch.stack(cols6[2:6], 1).flatten()]).to(torch.int32)
+                blk = blk.pin_memory().to(device, non_blocking=True)
+                pos, reg = blk[:2 * n].view(n, 2), blk[2 * n:].view(n, 4)
+            plane = torch.as_tensor(batch["pair"]).flatten().to(device=device, dtype=torch.int32).contiguous()
+            if mean.numel() != n or pos.shape[0] != n or plane.numel() != n:
+                raise ValueError("batch dict fields must hold one value per tile")
+            aug, log2_variants = None, 0
+            if "tta" in batch:                  # as predict_linear_blend: a tile's len(dataset.tta) variants follow each other
+                tta = getattr(ds, "tta", None)
+                variants = 0 if tta is None else len(tta)
+                if variants not in (1, 2, 4, 8, 16):
+                    raise ValueError("a batch with a 'tta' column needs dataset.tta = the 1, 2, 4, 8 or 16 variant codes of a tile")
+                log2_variants = variants.bit_length() - 1
+                aug = torch.as_tensor(batch["tta"]).flatten().to(device=device, dtype=torch.int32).contiguous()
+                if aug.numel() != n:
+                    raise ValueError("batch dict fields must hold one value per tile")
+            with _lib.device_of(raster):
+                ops.blend_accumulate(y_pred.contiguous(), mean.contiguous(), std.contiguous(), pos.contiguous(),
+                                     reg.contiguous(), tile_size, stride, raster, aug=aug, log2_variants=log2_variants,
+                                     plane=plane, n_planes=n_pairs)
+    want_spread = ops.SPREAD_MODES[spread] != 0
+    planes_out = 1 + int(want_spread) + (n_pairs if return_pairs else 0)
+    reuse = isinstance(host, str) and host == "reuse"
+    if reuse:
+        host = _host_cache.get((planes_out, rows, cols))
+    if not isinstance(host, _PairHost) or host.key != (planes_out, rows, cols):
+        host = _PairHost(planes_out, rows, cols)
+        if reuse:
+            _host_cache[host.key] = host
+    with _lib.device_of(raster):
+        # the fuse runs once, after the last blend: per pixel, so no order of the sweep can show in its bits
+        fused, spr = ops.fuse_planes(raster, fuse, spread)
+        dst = host.t
+        dst[0].copy_(fused, non_blocking=True)
+        if want_spread:
+            dst[1].copy_(spr, non_blocking=True)
+        if return_pairs:
+            dst[1 + int(want_spread):].copy_(raster, non_blocking=True)
+        torch.cuda.current_stream(device).synchronize()
+    out = host.t.numpy()
+    return PairSweep(out[0], out[1] if want_spread else None, out[1 + int(want_spread):] if return_pairs else None,
+                     getattr(ds, "image_pairs", None), host)

@@ -316,6 +316,9 @@ def predict_linear_blend(dataloader, model, reduce_to_rank0: bool = True, host=N
                 pos = pos - lo_t
             if mean.numel() != n or pos.shape[0] != n:
                 raise ValueError("batch dict fields must hold one value per tile")
+            if "pair" in batch:
+                raise ValueError("predict_linear_blend holds one raster: a loader that sweeps its image pairs (the 'pair' batch "
+                                 "column, GpuGridTiles(sweep_pairs=True)) goes to resdepth_amd.predict_pairs_linear_blend")
             aug, log2_variants = None, 0
             if "tta" in batch:
                 # test-time augmentation (GpuGridTiles(tta=...), or a host loader that supplies the same column and

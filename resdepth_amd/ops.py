@@ -743,16 +743,23 @@ def nhwc_to_nchw(x):
     return out
 
 
-def blend_accumulate(pred, mean, std, pos, reg, tile_size, stride, raster, aug=None, log2_variants=0):
+def blend_accumulate(pred, mean, std, pos, reg, tile_size, stride, raster, aug=None, log2_variants=0, plane=None,
+                     plane_stride=0, n_planes=1):
     """raster (float64 [rows, cols], device) += blend-weighted de-normalised tiles; pos/reg int32 device tensors.
     aug (int32 [n], device: the orientation code of every prediction, tiling.tta_codes) and log2_variants (0..4): test-time
     augmentation -- every prediction is turned back into the raster's orientation and weighs 2^-log2_variants
-    (rd_blend_accumulate_tta); without them the call is rd_blend_accumulate."""
+    (rd_blend_accumulate_tta); without them the call is rd_blend_accumulate.
+    plane (int32 [n], device) / n_planes / plane_stride: raster is float64 [n_planes, rows, cols] (or [rows, cols] with
+    n_planes = 1) and sample i goes into plane plane[i]; plane_stride (in doubles, 0 = rows * cols) is the distance between
+    planes (rd_blend_accumulate_planes: every plane gets the bits the call above gives its samples alone)."""
     n = pred.shape[0]
-    rows, cols = raster.shape
+    rows, cols = raster.shape[-2:]
     if raster.dtype != torch.float64 or pos.dtype != torch.int32 or reg.dtype != torch.int32:
         raise TypeError("blend_accumulate: raster must be float64, pos/reg int32")
-    if aug is None and int(log2_variants) == 0:
+    planes = plane is not None or int(n_planes) != 1 or int(plane_stride) != 0
+    if raster.dim() != 2 and not (raster.dim() == 3 and planes):
+        raise ValueError("blend_accumulate: raster must be [rows, cols], or [n_planes, rows, cols] with plane / n_planes")
+    if aug is None and int(log2_variants) == 0 and not planes:
         check(load().rd_blend_accumulate(ptr(_f32(pred, "pred")), ptr(mean), ptr(std), ptr(pos), ptr(reg), n, tile_size,
                                          stride, ptr(raster), rows, cols, stream_ptr()), "blend_accumulate")
         return raster
@@ -760,7 +767,56 @@ def blend_accumulate(pred, mean, std, pos, reg, tile_size, stride, raster, aug=N
         raise TypeError("blend_accumulate: aug must be int32 with one code per tile")
     if tuple(pred.shape[-2:]) != (tile_size, tile_size):
         raise ValueError("blend_accumulate: oriented predictions must be tile_size x tile_size")
-    check(load().rd_blend_accumulate_tta(ptr(_f32(pred, "pred")), ptr(mean), ptr(std), ptr(pos), ptr(reg), ptr(aug), n,
-                                         tile_size, stride, int(log2_variants), ptr(raster), rows, cols, stream_ptr()),
-          "blend_accumulate_tta")
+    if not planes:
+        check(load().rd_blend_accumulate_tta(ptr(_f32(pred, "pred")), ptr(mean), ptr(std), ptr(pos), ptr(reg), ptr(aug), n,
+                                             tile_size, stride, int(log2_variants), ptr(raster), rows, cols, stream_ptr()),
+              "blend_accumulate_tta")
+        return raster
+    if plane is not None and (plane.dtype != torch.int32 or plane.numel() != n):
+        raise TypeError("blend_accumulate: plane must be int32 with one index per tile")
+    ps = int(plane_stride) if int(plane_stride) else rows * cols
+    if not raster.is_contiguous() or (raster.dim() == 3 and (raster.shape[0] != int(n_planes) or ps != rows * cols)):
+        raise ValueError("blend_accumulate: a [n_planes, rows, cols] raster must be contiguous and match n_planes / plane_stride")
+    if raster.dim() == 2 and int(n_planes) != 1:
+        raise ValueError("blend_accumulate: n_planes > 1 needs a [n_planes, rows, cols] raster")
+    check(load().rd_blend_accumulate_planes(ptr(_f32(pred, "pred")), ptr(mean), ptr(std), ptr(pos), ptr(reg), ptr(aug),
+                                            ptr(plane), n, tile_size, stride, int(log2_variants), ptr(raster), int(n_planes), ps,
+                                            rows, cols, stream_ptr()), "blend_accumulate_planes")
     return raster
+
+
+FUSE_MODES = {"mean": 0, "median": 1}               # RD_FUSE_*
+SPREAD_MODES = {None: 0, "none": 0, "range": 1, "std": 2}      # RD_SPREAD_*
+
+
+def fuse_planes(planes, fuse="median", spread=None, fused_out=None, spread_out=None):
+    """Per-pixel fusion of P = planes.shape[0] (1..16) float64 device rasters [P, ...] of one surface -> (fused, spread or
+    None), each of the planes' trailing shape (rd_fuse_planes).  fuse: "mean" (v_0 + v_1 + ... in plane order, divided by P)
+    or "median" (np.median's: the middle order statistic, or (a + b) * 0.5 of the two middle ones); spread: None, "range"
+    (max - min) or "std" (sqrt(sum (v - mean)^2 / P)).  A NaN in any plane gives NaN in every output of that pixel.  `planes`
+    may be a strided view along its first axis (e.g. rows of a larger buffer) as long as each plane is contiguous."""
+    if fuse not in FUSE_MODES:
+        raise ValueError(f"fuse_planes: fuse must be one of {sorted(FUSE_MODES)} (got {fuse!r})")
+    if spread not in SPREAD_MODES:
+        raise ValueError(f"fuse_planes: spread must be None, 'range' or 'std' (got {spread!r})")
+    if planes.dtype != torch.float64 or not planes.is_cuda or planes.dim() < 2:
+        raise TypeError("fuse_planes: planes must be a float64 device tensor [P, ...]")
+    p, shape = planes.shape[0], tuple(planes.shape[1:])
+    n = planes[0].numel()
+    if p < 1 or n < 1 or not planes[0].is_contiguous():
+        raise ValueError("fuse_planes: every plane must be contiguous and non-empty")
+    stride = planes.stride(0) if p > 1 else n
+    want = SPREAD_MODES[spread] != 0
+    outs = []
+    for name, t, needed in (("fused_out", fused_out, True), ("spread_out", spread_out, want)):
+        if not needed:
+            outs.append(None)
+            continue
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float64, device=planes.device)
+        elif t.dtype != torch.float64 or t.device != planes.device or t.numel() != n or not t.is_contiguous():
+            raise TypeError(f"fuse_planes: {name} must be a contiguous float64 tensor of a plane's size on the planes' device")
+        outs.append(t)
+    check(load().rd_fuse_planes(planes.data_ptr(), stride, p, n, FUSE_MODES[fuse], ptr(outs[0]), SPREAD_MODES[spread], ptr(outs[1]),
+                                stream_ptr()), "fuse_planes")
+    return outs[0], outs[1]

@@ -161,13 +161,16 @@ class GridTileSet:
     raster_shape, len(), `pos` in loader order, `shard` / `shard_plan`), plus the per-sample boxes and pair indices."""
 
     def __init__(self, tile_size, stride, raster_shape, pos, reg, pair_idx, shard, shard_plan, tta=None, tta_code=None,
-                 tta_swap=None):
+                 tta_swap=None, n_pairs=None, image_pairs=None):
         self.tile_size, self.stride, self.raster_shape = int(tile_size), int(stride), tuple(raster_shape)
         self.pos, self.reg, self.pair_idx = pos, reg, pair_idx
         self.shard, self.shard_plan = shard, shard_plan
         # test-time augmentation (GpuGridTiles(tta=...)): `tta` = the variant codes -- every tile is len(tta) consecutive
         # samples --, tta_code / tta_swap = orientation code and view-swap flag of every sample.  All None without it.
         self.tta, self.tta_code, self.tta_swap = tta, tta_code, tta_swap
+        # all pairs in one sweep (GpuGridTiles(sweep_pairs=True)): n_pairs = len(image_pairs), and pair_idx[i] is the plane of
+        # sample i.  Both None without it (pair_idx is then all 0: a 'test' sweep reads pair 0).
+        self.n_pairs, self.image_pairs = n_pairs, image_pairs
 
     def __len__(self):
         return len(self.pos)
@@ -198,12 +201,20 @@ class GpuGridTiles:
     int32 device column "tta" (the orientation code of every sample), `input` in that orientation with the PLAIN tile's
     dsm_mean, and NO target / loss_mask: the variants are for prediction.  predict_linear_blend turns every prediction back
     and averages a tile's variants with the exact weight 1 / variants (rd_blend_accumulate_tta); the sweep costs variants x
-    tiles forwards.  tta=None and tta_swap_views=False: the loader is what it was (rd_assemble_grid_tiles, no "tta" column)."""
+    tiles forwards.  tta=None and tta_swap_views=False: the loader is what it was (rd_assemble_grid_tiles, no "tta" column).
+
+    sweep_pairs (strategy 'test' only, an input with image views): every tile is repeated once per entry of `image_pairs`
+    (1..16 of them), tile-major and pair-minor (tiling.pair_expand; with tta: tile, then pair, then variant), so ONE sweep
+    predicts the raster from every pair -- ensemble.predict_pairs_linear_blend blends pair p into plane p and fuses the
+    planes on the device.  Batches carry the int32 device column "pair" (the index into image_pairs = the plane of every
+    sample) and, as under tta, NO target / loss_mask; `dataset` gains n_pairs and image_pairs, and its pair_idx is the
+    column.  Not with shard of world > 1: the banded multi-GPU delivery is written for one plane.  False: the loader is what
+    it was (pair 0 at every position, no "pair" column)."""
 
     def __init__(self, sampler: GpuPatchSampler, strategy: str, area_defn, input_channels: str = "geom-stereo",
                  image_pairs=None, stride=None, dsm_mean=None, transform_dsm: bool = True, transform_orthos: bool = True,
                  batch_size: int = 32, shard=(0, 1), prefetch: int = 1, augment: bool = False,
-                 permute_images_within_pair: bool = False, tta=None, tta_swap_views: bool = False):
+                 permute_images_within_pair: bool = False, tta=None, tta_swap_views: bool = False, sweep_pairs: bool = False):
         if augment:
             raise ValueError("GpuGridTiles: augment=True is not supported (the reference augments 'train' samples only)")
         if permute_images_within_pair:
@@ -221,6 +232,17 @@ class GpuGridTiles:
             raise ValueError(f"GpuGridTiles: strategy must be 'val' or 'test' (got {strategy!r}); 'train' is SamplerLoader")
         if strategy == "val" and sampler.dsm_gt is None:
             raise ValueError("GpuGridTiles: strategy='val' needs the sampler's ground-truth raster")
+        self.sweep_pairs = bool(sweep_pairs)
+        if self.sweep_pairs:
+            if strategy != "test":
+                raise ValueError("GpuGridTiles: sweep_pairs is for strategy='test' (prediction); 'val' already reads every pair")
+            if input_channels not in _VIEW_CHANNELS:
+                raise ValueError(f"GpuGridTiles: sweep_pairs needs an input with image views (got input_channels={input_channels!r})")
+            if image_pairs is not None and len(image_pairs) > tiling.MAX_SWEEP_PAIRS:
+                raise ValueError(f"GpuGridTiles: sweep_pairs takes up to {tiling.MAX_SWEEP_PAIRS} image pairs (got {len(image_pairs)})")
+            if world > 1:
+                raise ValueError("GpuGridTiles: sweep_pairs with a shard of world > 1 is not supported (the banded multi-GPU "
+                                 "delivery holds one plane)")
         self.source = sampler                 # not `.sampler`: predict_linear_blend reads that name as a torch sampler
         t = sampler.tile
         if t % 8:
@@ -251,6 +273,14 @@ class GpuGridTiles:
         if not 0 < stride <= t:
             raise ValueError(f"GpuGridTiles: stride must be in 1..{t} (got {stride})")
         pos, reg, pair_idx, plan = tiling.grid_shard(strategy, pos, reg, pair_idx, t, sampler.h, (rank, world))
+        extra = {}
+        if self.sweep_pairs:
+            pos, reg, pair_idx = tiling.pair_expand(pos, reg, len(pairs))
+            extra = dict(n_pairs=len(pairs), image_pairs=[list(pr) for pr in pairs])
+            if sampler.dsm_gt is not None and tta is None and not tta_swap_views:
+                warnings.warn("GpuGridTiles: with sweep_pairs the batches carry no target / loss_mask (the sampler's ground "
+                              "truth is not read); use a loader without it where a loss or a per-tile metric is needed",
+                              stacklevel=2)
         self.tta = tta is not None or bool(tta_swap_views)
         if self.tta:
             if strategy != "test":
@@ -267,10 +297,10 @@ class GpuGridTiles:
                 rows6 = [p + len(pairs) * sw for p, sw in zip(pair_idx, swap)]
                 pairs = pairs + [pr[::-1] for pr in pairs]
             self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan, variants,
-                                       code, swap)
+                                       code, swap, **extra)
         else:
             rows6 = pair_idx
-            self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan)
+            self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan, **extra)
         # transform modes of rd_assemble_grid_tiles: 0 raw, 1 the given mean, 2 the tile's mean (`not mean`: the reference's test)
         self.dsm_mode = 0 if not transform_dsm else (2 if not dsm_mean else 1)
         self.dsm_mean = float(dsm_mean) if self.dsm_mode == 1 else 0.0
@@ -288,6 +318,7 @@ class GpuGridTiles:
         self._table = tab.to(dev)
         self._pair_planes = torch.tensor(pairs, dtype=torch.int32).to(dev) if views else None
         self._aug = torch.tensor(self.dataset.tta_code, dtype=torch.int32).reshape(-1).to(dev) if self.tta else None
+        self._pair = torch.tensor(pair_idx, dtype=torch.int32).reshape(-1).to(dev) if self.sweep_pairs else None
         self._meta = {k: tab[:n, c].to(torch.int64).to(dev) for c, k in enumerate(
             ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
              "patch_valid_pixels_lrx"))}
@@ -310,7 +341,8 @@ class GpuGridTiles:
         inp = torch.empty(n, c, t, t, dtype=torch.float32, device=dev)
         mean = torch.empty(n, dtype=torch.float32, device=dev)
         tgt = msk = None
-        if src.dsm_gt is not None and not self.tta:      # oriented samples are for prediction: no target / loss_mask
+        # oriented samples and the samples of a pair sweep are for prediction: no target / loss_mask
+        if src.dsm_gt is not None and not self.tta and not self.sweep_pairs:
             tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
             msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
         lib = load()
@@ -329,6 +361,8 @@ class GpuGridTiles:
             check(lib.rd_assemble_grid_tiles_aug(*head, ptr(batch["tta"]), *tail), "assemble_grid_tiles_aug")
         else:
             check(lib.rd_assemble_grid_tiles(*head, *tail), "assemble_grid_tiles")
+        if self.sweep_pairs:
+            batch["pair"] = self._pair[k0:k1]
         for key, col in self._meta.items():
             batch[key] = col[k0:k1]
         if tgt is not None:

@@ -237,6 +237,23 @@ def tta_expand(pos, reg, pair_idx, codes, swap_views: bool = False):
             tuple(c for c, _ in variants))
 
 
+# ---- all image pairs of a raster in one sweep ---------------------------------------------------------------------------
+MAX_SWEEP_PAIRS = 16        # rd_fuse_planes reduces up to 16 planes per pixel
+
+
+def pair_expand(pos, reg, n_pairs: int):
+    """A 'test' sample list with every tile repeated once per image pair, tile-major and pair-minor -> (pos, reg, pair index
+    per sample).  The idea of `tta_expand`: a tile's n_pairs samples are neighbours, so its DSM tile is hot in cache when the
+    next pair reads it, and the band plan and the frontier bookkeeping of the sweep see n_pairs samples where they saw one.
+    Applied AFTER grid_shard and BEFORE tta_expand: with test-time augmentation the order is tile-major, then pair, then
+    variant-minor.  The pair index is the plane of the sample in a one-pass sweep (ensemble.predict_pairs_linear_blend)."""
+    n_pairs = int(n_pairs)
+    if n_pairs < 1:
+        raise ValueError(f"pair_expand: n_pairs must be positive (got {n_pairs})")
+    rep = lambda xs: [x for x in xs for _ in range(n_pairs)]
+    return rep(pos), rep(reg), list(range(n_pairs)) * len(pos)
+
+
 # ---- the training set: sampling_strategy 'train' of the reference's `_determine_patches` (lib/DsmOrthoDataset.py:316-371) ----
 def _train_regions(area_defn, tile_size: int):
     """[(y_start, x_start, n_y, n_x)] per region of `area_defn`: the valid upper-left positions of

@@ -16,11 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .inference import _raster_shape
+from .inference import _raster_shape, _sweep_batch
 from .trainer import DevicePrefetcher
-
-_META = ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
-         "patch_valid_pixels_lrx")
 
 
 class PairSweep:
@@ -77,31 +74,10 @@ def predict_pairs_linear_blend(dataloader, model, fuse: str = "median", spread=N
             x = batch["input"].to(device, non_blocking=True)
             n = x.shape[0]
             y_pred = model(x)
-            mean = torch.as_tensor(batch["dsm_mean"]).flatten().to(torch.float32).to(device)
-            std = torch.as_tensor(batch["dsm_std"]).flatten().to(torch.float32).to(device)
-            # the metadata block of predict_linear_blend: device columns as they are, host columns as one pinned int32 block
-            cols6 = [torch.as_tensor(batch[k]).flatten() for k in _META]
-            if any(c.is_cuda for c in cols6):
-                cols6 = [c.to(device) for c in cols6]
-                pos = torch.stack(cols6[0:2], 1).to(torch.int32)
-                reg = torch.stack(cols6[2:6], 1).to(torch.int32)
-            else:
-                blk = torch.cat([torch.stack(cols6[0:2], 1).flatten(), torch.stack(cols6[2:6], 1).flatten()]).to(torch.int32)
-                blk = blk.pin_memory().to(device, non_blocking=True)
-                pos, reg = blk[:2 * n].view(n, 2), blk[2 * n:].view(n, 4)
+            mean, std, pos, reg, aug, log2_variants = _sweep_batch(batch, ds, device, n)
             plane = torch.as_tensor(batch["pair"]).flatten().to(device=device, dtype=torch.int32).contiguous()
-            if mean.numel() != n or pos.shape[0] != n or plane.numel() != n:
+            if plane.numel() != n:
                 raise ValueError("batch dict fields must hold one value per tile")
-            aug, log2_variants = None, 0
-            if "tta" in batch:                  # as predict_linear_blend: a tile's len(dataset.tta) variants follow each other
-                tta = getattr(ds, "tta", None)
-                variants = 0 if tta is None else len(tta)
-                if variants not in (1, 2, 4, 8, 16):
-                    raise ValueError("a batch with a 'tta' column needs dataset.tta = the 1, 2, 4, 8 or 16 variant codes of a tile")
-                log2_variants = variants.bit_length() - 1
-                aug = torch.as_tensor(batch["tta"]).flatten().to(device=device, dtype=torch.int32).contiguous()
-                if aug.numel() != n:
-                    raise ValueError("batch dict fields must hold one value per tile")
             with _lib.device_of(raster):
                 ops.blend_accumulate(y_pred.contiguous(), mean.contiguous(), std.contiguous(), pos.contiguous(),
                                      reg.contiguous(), tile_size, stride, raster, aug=aug, log2_variants=log2_variants,

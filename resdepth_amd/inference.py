@@ -28,6 +28,7 @@ import torch
 from torch.utils.data import Dataset
 
 from . import _lib, ops
+from .sampler import _META
 from .tiling import band_shards, regular_grid
 from .trainer import DevicePrefetcher
 
@@ -230,6 +231,39 @@ def _exchange_overlaps(raster, me, plan, cols, device):
 _host_cache = {}
 
 
+def _sweep_batch(batch, ds, device, n):
+    """The per-tile columns of one sweep batch of n tiles, on `device` -> mean, std (float32 [n]), pos (int32 [n, 2]: y, x),
+    reg (int32 [n, 4]), aug (int32 [n] or None), log2_variants."""
+    mean = torch.as_tensor(batch["dsm_mean"]).flatten().to(torch.float32).to(device)
+    std = torch.as_tensor(batch["dsm_std"]).flatten().to(torch.float32).to(device)
+    # device columns as they are; host columns (a DataLoader's) travel as ONE pinned int32 block per batch, asynchronously -- a
+    # pageable `.to(device)` per field would block the host behind everything already enqueued, once per field and batch
+    cols6 = [torch.as_tensor(batch[k]).flatten() for k in _META]
+    if any(c.is_cuda for c in cols6):
+        cols6 = [c.to(device) for c in cols6]
+        pos = torch.stack(cols6[0:2], 1).to(torch.int32)
+        reg = torch.stack(cols6[2:6], 1).to(torch.int32)
+    else:           # [pos (n x 2) | reg (n x 4)] in one pinned block, one asynchronous copy, two contiguous views
+        blk = torch.cat([torch.stack(cols6[0:2], 1).flatten(), torch.stack(cols6[2:6], 1).flatten()]).to(torch.int32)
+        blk = blk.pin_memory().to(device, non_blocking=True)
+        pos, reg = blk[:2 * n].view(n, 2), blk[2 * n:].view(n, 4)
+    if mean.numel() != n or pos.shape[0] != n:
+        raise ValueError("batch dict fields must hold one value per tile")
+    aug, log2_variants = None, 0
+    if "tta" in batch:
+        # test-time augmentation (GpuGridTiles(tta=...), or a host loader that supplies the same column and
+        # `dataset.tta`): sample i is oriented by code tta[i], and a tile's len(dataset.tta) variants follow each other
+        tta = getattr(ds, "tta", None)                # a tuple here, any sequence or array from a host dataset
+        variants = 0 if tta is None else len(tta)
+        if variants not in (1, 2, 4, 8, 16):
+            raise ValueError("a batch with a 'tta' column needs dataset.tta = the 1, 2, 4, 8 or 16 variant codes of a tile")
+        log2_variants = variants.bit_length() - 1
+        aug = torch.as_tensor(batch["tta"]).flatten().to(device=device, dtype=torch.int32).contiguous()
+        if aug.numel() != n:
+            raise ValueError("batch dict fields must hold one value per tile")
+    return mean, std, pos, reg, aug, log2_variants
+
+
 def predict_linear_blend(dataloader, model, reduce_to_rank0: bool = True, host=None):
     """-> np.ndarray [rows, cols] float64 (lib/evaluation.py:460-513).  With a process group: every rank sweeps its shard of
     the tiles and the complete raster is returned on rank 0 (band plan: on every rank -- they share the host array);
@@ -290,47 +324,19 @@ def predict_linear_blend(dataloader, model, reduce_to_rank0: bool = True, host=N
     front = _frontiers(tile_rows, tile_size, rows) if tile_rows is not None else None
     done = 0
     # host batches (a DataLoader's): input / dsm_mean / dsm_std of batch k + 1 go to the device on a copy stream while batch k
-    # computes (trainer.DevicePrefetcher; device-resident batches pass through untouched); the per-tile offsets and valid-pixel
-    # boxes travel as ONE pinned int32 block per batch, asynchronously -- a pageable `.to(device)` per field would block the host
-    # behind everything already enqueued, once per field and batch
-    meta_keys = ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
-                 "patch_valid_pixels_lrx")
+    # computes (trainer.DevicePrefetcher; device-resident batches pass through untouched)
     lo_t = torch.tensor([lo, 0], dtype=torch.int32, device=device) if lo else None
     with torch.no_grad():
         for batch in DevicePrefetcher(dataloader, device, 1):
             x = batch["input"].to(device, non_blocking=True)
             n = x.shape[0]
             y_pred = model(x)
-            mean = torch.as_tensor(batch["dsm_mean"]).flatten().to(torch.float32).to(device)
-            std = torch.as_tensor(batch["dsm_std"]).flatten().to(torch.float32).to(device)
-            cols6 = [torch.as_tensor(batch[k]).flatten() for k in meta_keys]
-            if any(c.is_cuda for c in cols6):
-                cols6 = [c.to(device) for c in cols6]
-                pos = torch.stack(cols6[0:2], 1).to(torch.int32)
-                reg = torch.stack(cols6[2:6], 1).to(torch.int32)
-            else:           # [pos (n x 2) | reg (n x 4)] in one pinned block, one asynchronous copy, two contiguous views
-                blk = torch.cat([torch.stack(cols6[0:2], 1).flatten(), torch.stack(cols6[2:6], 1).flatten()]).to(torch.int32)
-                blk = blk.pin_memory().to(device, non_blocking=True)
-                pos, reg = blk[:2 * n].view(n, 2), blk[2 * n:].view(n, 4)
-            if lo_t is not None:
-                pos = pos - lo_t
-            if mean.numel() != n or pos.shape[0] != n:
-                raise ValueError("batch dict fields must hold one value per tile")
             if "pair" in batch:
                 raise ValueError("predict_linear_blend holds one raster: a loader that sweeps its image pairs (the 'pair' batch "
                                  "column, GpuGridTiles(sweep_pairs=True)) goes to resdepth_amd.predict_pairs_linear_blend")
-            aug, log2_variants = None, 0
-            if "tta" in batch:
-                # test-time augmentation (GpuGridTiles(tta=...), or a host loader that supplies the same column and
-                # `dataset.tta`): sample i is oriented by code tta[i], and a tile's len(dataset.tta) variants follow each other
-                tta = getattr(ds, "tta", None)                # a tuple here, any sequence or array from a host dataset
-                variants = 0 if tta is None else len(tta)
-                if variants not in (1, 2, 4, 8, 16):
-                    raise ValueError("a batch with a 'tta' column needs dataset.tta = the 1, 2, 4, 8 or 16 variant codes of a tile")
-                log2_variants = variants.bit_length() - 1
-                aug = torch.as_tensor(batch["tta"]).flatten().to(device=device, dtype=torch.int32).contiguous()
-                if aug.numel() != n:
-                    raise ValueError("batch dict fields must hold one value per tile")
+            mean, std, pos, reg, aug, log2_variants = _sweep_batch(batch, ds, device, n)
+            if lo_t is not None:
+                pos = pos - lo_t
             with _lib.device_of(raster):
                 ops.blend_accumulate(y_pred.contiguous(), mean.contiguous(), std.contiguous(), pos.contiguous(),
                                      reg.contiguous(), tile_size, stride, raster, aug=aug, log2_variants=log2_variants)

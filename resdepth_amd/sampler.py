@@ -10,10 +10,80 @@ from __future__ import annotations
 
 import warnings
 
+import numpy as np
 import torch
 
 from . import tiling
 from ._lib import check, load, ptr, stream_ptr
+
+# the per-tile metadata columns of a batch dict, in the column order of the loaders' tables ([pos (y, x) | box])
+_META = ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
+         "patch_valid_pixels_lrx")
+_VIEW_CHANNELS = ("geom-mono", "geom-stereo", "geom-multiview", "stereo")
+
+
+def _transform_mode(enabled, mean):
+    """(mode, mean) of a DSM / ortho transform as the assembly kernels take it: 0 raw, 1 the given mean, 2 each tile's own mean
+    (`not mean`, None or 0.0: the reference's test)."""
+    mode = 0 if not enabled else (2 if not mean else 1)
+    return mode, (float(mean) if mode == 1 else 0.0)
+
+
+def _aug_code(aug, n=-1):
+    """int [n, 3] (k, flip_v, flip_h), a tensor or anything numpy reads -> int32 [n] orientation codes k | flip_v << 2 |
+    flip_h << 3 of the same kind (tiling.tta_codes: the one encoding of every loader and kernel)."""
+    a = aug.to(torch.int32) if torch.is_tensor(aug) else np.asarray(aug, dtype=np.int32)
+    a = a.reshape(n, 3)
+    return a[:, 0] | (a[:, 1] << 2) | (a[:, 2] << 3)
+
+
+def _draw_aug(n, generator):
+    """The reference's augmentation draws for n samples -> int64 [n, 3]: k in {0..3}, then flip_v, then flip_h (each with
+    probability 1/2).  This order of the three draws is what makes a seeded generator reproduce a run."""
+    return torch.stack([torch.randint(0, 4, (n,), generator=generator), torch.randint(0, 2, (n,), generator=generator),
+                        torch.randint(0, 2, (n,), generator=generator)], 1)
+
+
+def _queued(jobs, produce, depth):
+    """The loaders' queue: `produce(job)` runs max(0, depth) jobs ahead of the item handed out, in job order; the queue is
+    drained at the end.  min(n_jobs, k + depth + 1) jobs are produced when item k is yielded."""
+    queue = []
+    for job in jobs:
+        queue.append(produce(job))
+        if len(queue) > max(0, int(depth)):
+            yield queue.pop(0)
+    while queue:
+        yield queue.pop(0)
+
+
+def _prefetched(device, jobs, assemble, depth, side=None):
+    """Generator of `assemble(job)` (a batch dict) for every job, assembled `depth` batches AHEAD on a side stream (`side`, or a
+    fresh one) and handed to the consumer's stream in job order (_hand_over): the prefetch of every loader of this module."""
+    if side is None:
+        with torch.cuda.device(device):
+            side = torch.cuda.Stream(device=device)
+
+    def produce(job):
+        with torch.cuda.device(device), torch.cuda.stream(side):
+            b = assemble(job)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        return b, ev
+
+    for item in _queued(jobs, produce, depth):
+        yield _hand_over(device, item)
+
+
+def _hand_over(device, item):
+    """(batch, event recorded behind its assembly) -> the batch, safe to use on `device`'s current stream: that stream waits
+    on the one event, and every device tensor of the dict is pinned to it with `record_stream`."""
+    b, ev = item
+    cur = torch.cuda.current_stream(device)
+    cur.wait_event(ev)
+    for v in b.values():
+        if torch.is_tensor(v) and v.is_cuda:
+            v.record_stream(cur)
+    return b
 
 
 class GpuPatchSampler:
@@ -65,8 +135,7 @@ class GpuPatchSampler:
                 omean = torch.full((n,), float(self.ortho_mean), dtype=torch.float32, device=dev)
         aug_t = None
         if aug is not None:
-            a = torch.as_tensor(aug, dtype=torch.int32).reshape(n, 3)
-            aug_t = (a[:, 0] | (a[:, 1] << 2) | (a[:, 2] << 3)).to(torch.int32).to(dev).contiguous()
+            aug_t = _aug_code(torch.as_tensor(aug, dtype=torch.int32), n).to(dev).contiguous()
         inp = torch.empty(n, 1 + v, t, t, dtype=torch.float32, device=dev)
         tgt = msk = None
         if self.dsm_gt is not None:
@@ -89,10 +158,7 @@ class GpuPatchSampler:
         g = generator
         ys = torch.randint(0, self.h - self.tile + 1, (n,), generator=g)
         xs = torch.randint(0, self.w - self.tile + 1, (n,), generator=g)
-        aug = None
-        if augment:
-            aug = torch.stack([torch.randint(0, 4, (n,), generator=g), torch.randint(0, 2, (n,), generator=g),
-                               torch.randint(0, 2, (n,), generator=g)], 1)
+        aug = _draw_aug(n, g) if augment else None
         pair = torch.as_tensor(pairs, dtype=torch.int32)
         if pair.dim() == 1:
             pair = pair.unsqueeze(0).expand(n, -1)
@@ -104,31 +170,8 @@ class GpuPatchSampler:
         forward / backward instead of in front of its own: the consumer's stream waits on one event per batch and the tensors
         are pinned to it with `record_stream`.  The positions / augmentation draws come from `generator` in the same order as
         consecutive `random_batch` calls, so the stream of batches is the same with or without prefetch."""
-        side = torch.cuda.Stream(device=self.device)
-        queue = []
-
-        def produce():
-            with torch.cuda.stream(side):
-                b = self.random_batch(batch_size, pairs, generator=generator, augment=augment)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            return b, ev
-
-        for k in range(n_batches):
-            queue.append(produce())
-            if len(queue) > max(0, int(prefetch)):
-                yield self._hand_over(queue.pop(0))
-        while queue:
-            yield self._hand_over(queue.pop(0))
-
-    def _hand_over(self, item):
-        b, ev = item
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(ev)
-        for v in b.values():
-            if torch.is_tensor(v) and v.is_cuda:
-                v.record_stream(cur)
-        return b
+        return _prefetched(self.device, range(n_batches),
+                           lambda k: self.random_batch(batch_size, pairs, generator=generator, augment=augment), prefetch)
 
 
 class SamplerLoader:
@@ -153,7 +196,29 @@ class SamplerLoader:
                                            augment=self.augment, prefetch=self.prefetch)
 
 
-_VIEW_CHANNELS = ("geom-mono", "geom-stereo", "geom-multiview", "stereo")
+def _check_channels(who, input_channels):
+    """-> does the input carry image views?"""
+    if input_channels not in ("geom",) + _VIEW_CHANNELS:
+        raise ValueError(f"{who}: unknown input_channels {input_channels!r}")
+    return input_channels in _VIEW_CHANNELS
+
+
+def _check_shard(who, shard):
+    rank, world = int(shard[0]), int(shard[1])
+    if not 0 <= rank < world:
+        raise ValueError(f"{who}: bad shard {shard!r}")
+    return rank, world
+
+
+def _check_image_pairs(who, sampler, image_pairs, where=""):
+    """image_pairs as int lists: all of one length >= 1, every entry a plane of the sampler's orthos."""
+    pairs = [[int(p) for p in pr] for pr in image_pairs]
+    if len({len(p) for p in pairs}) != 1 or not pairs[0]:
+        raise ValueError(f"{who}: every image pair must have the same number of views")
+    n_planes = sampler.orthos.shape[0]
+    if any(p < 0 or p >= n_planes for pr in pairs for p in pr):
+        raise ValueError(f"{who}: an image index is outside the {n_planes} ortho planes{where}")
+    return pairs
 
 
 class GridTileSet:
@@ -221,11 +286,8 @@ class GpuGridTiles:
             raise ValueError("GpuGridTiles: permute_images_within_pair=True is not supported")
         if not isinstance(sampler, GpuPatchSampler):
             raise ValueError("GpuGridTiles takes one GpuPatchSampler (multi-dataset ConcatDatasets are not supported)")
-        if input_channels not in ("geom",) + _VIEW_CHANNELS:
-            raise ValueError(f"GpuGridTiles: unknown input_channels {input_channels!r}")
-        rank, world = int(shard[0]), int(shard[1])
-        if not 0 <= rank < world:
-            raise ValueError(f"GpuGridTiles: bad shard {shard!r}")
+        views = _check_channels("GpuGridTiles", input_channels)
+        rank, world = _check_shard("GpuGridTiles", shard)
         if strategy == "val" and world > 1:
             raise ValueError("GpuGridTiles: a sharded validation set is not supported")
         if strategy not in ("val", "test"):
@@ -236,7 +298,7 @@ class GpuGridTiles:
         if self.sweep_pairs:
             if strategy != "test":
                 raise ValueError("GpuGridTiles: sweep_pairs is for strategy='test' (prediction); 'val' already reads every pair")
-            if input_channels not in _VIEW_CHANNELS:
+            if not views:
                 raise ValueError(f"GpuGridTiles: sweep_pairs needs an input with image views (got input_channels={input_channels!r})")
             if image_pairs is not None and len(image_pairs) > tiling.MAX_SWEEP_PAIRS:
                 raise ValueError(f"GpuGridTiles: sweep_pairs takes up to {tiling.MAX_SWEEP_PAIRS} image pairs (got {len(image_pairs)})")
@@ -247,17 +309,11 @@ class GpuGridTiles:
         t = sampler.tile
         if t % 8:
             raise ValueError(f"GpuGridTiles: tile_size must be a multiple of 8 (got {t})")
-        views = input_channels in _VIEW_CHANNELS
         pairs = None
         if views:
             if sampler.orthos is None or not image_pairs:
                 raise ValueError(f"GpuGridTiles: input_channels={input_channels!r} needs the sampler's orthos and image_pairs")
-            pairs = [[int(p) for p in pr] for pr in image_pairs]
-            if len({len(p) for p in pairs}) != 1 or not pairs[0]:
-                raise ValueError("GpuGridTiles: every image pair must have the same number of views")
-            n_planes = sampler.orthos.shape[0]
-            if any(p < 0 or p >= n_planes for pr in pairs for p in pr):
-                raise ValueError(f"GpuGridTiles: an image index is outside the {n_planes} ortho planes")
+            pairs = _check_image_pairs("GpuGridTiles", sampler, image_pairs)
         self.strategy, self.input_channels = strategy, input_channels
         self.views = len(pairs[0]) if views else 0
         self.dsm_channel = 0 if input_channels == "stereo" else 1
@@ -302,11 +358,8 @@ class GpuGridTiles:
             rows6 = pair_idx
             self.dataset = GridTileSet(t, stride, (sampler.h, sampler.w), pos, reg, pair_idx, (rank, world), plan, **extra)
         # transform modes of rd_assemble_grid_tiles: 0 raw, 1 the given mean, 2 the tile's mean (`not mean`: the reference's test)
-        self.dsm_mode = 0 if not transform_dsm else (2 if not dsm_mean else 1)
-        self.dsm_mean = float(dsm_mean) if self.dsm_mode == 1 else 0.0
-        om = sampler.ortho_mean
-        self.ortho_mode = 0 if not transform_orthos else (2 if not om else 1)
-        self.ortho_mean = float(om) if self.ortho_mode == 1 else 0.0
+        self.dsm_mode, self.dsm_mean = _transform_mode(transform_dsm, dsm_mean)
+        self.ortho_mode, self.ortho_mean = _transform_mode(transform_orthos, sampler.ortho_mean)
         dev = sampler.device
         n = len(pos)
         tab = torch.zeros(max(n, 1), 8, dtype=torch.int32)
@@ -319,9 +372,7 @@ class GpuGridTiles:
         self._pair_planes = torch.tensor(pairs, dtype=torch.int32).to(dev) if views else None
         self._aug = torch.tensor(self.dataset.tta_code, dtype=torch.int32).reshape(-1).to(dev) if self.tta else None
         self._pair = torch.tensor(pair_idx, dtype=torch.int32).reshape(-1).to(dev) if self.sweep_pairs else None
-        self._meta = {k: tab[:n, c].to(torch.int64).to(dev) for c, k in enumerate(
-            ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
-             "patch_valid_pixels_lrx"))}
+        self._meta = {k: tab[:n, c].to(torch.int64).to(dev) for c, k in enumerate(_META)}
         self.drop_last = False
 
     def __len__(self):
@@ -376,27 +427,85 @@ class GpuGridTiles:
             with torch.cuda.stream(side):
                 ws = torch.empty(load().rd_assemble_grid_tiles_ws_bytes(self.batch_size, src.tile), dtype=torch.uint8,
                                  device=src.device)
-        queue = []
-
-        def produce(k0, k1):
-            with torch.cuda.device(src.device), torch.cuda.stream(side):
-                b = self._assemble(k0, k1, ws)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            return b, ev
-
-        for k0, k1 in tiling.batch_bounds(len(self.dataset), self.batch_size):
-            queue.append(produce(k0, k1))
-            if len(queue) > max(0, self.prefetch):
-                yield src._hand_over(queue.pop(0))
-        while queue:
-            yield src._hand_over(queue.pop(0))
+        yield from _prefetched(src.device, tiling.batch_bounds(len(self.dataset), self.batch_size),
+                               lambda k: self._assemble(k[0], k[1], ws), self.prefetch, side)
 
 
 _RASTER_DESC = [("dsm_in", "<u8"), ("dsm_gt", "<u8"), ("ortho", "<u8"), ("height", "<i4"), ("width", "<i4"), ("n_planes", "<i4"),
                 ("nodata", "<f4"), ("dsm_std", "<f4"), ("ortho_mode", "<i4"), ("ortho_mean", "<f4"), ("ortho_std", "<f4"),
                 ("reserved", "<i4", (2,))]          # rd_train_raster (include/resdepth_hip.h), 64 bytes
 _SAMPLE_INTS = 8                                    # RD_TRAIN_SAMPLE_INTS
+_TRAIN_AUG_BOX = 16                                 # RD_TRAIN_AUG_BOX
+
+
+def _f32bits(v):
+    return int(np.array(v, dtype=np.float32).view(np.int32))
+
+
+def _check_loader_args(who, datasets, input_channels, batch_size, shard):
+    """The checks GpuTrainSet and GpuValSet share -> datasets (a list), their samplers, views (does the input carry image
+    views?), (rank, world)."""
+    if isinstance(datasets, dict):
+        datasets = [datasets]
+    if not datasets:
+        raise ValueError(f"{who}: no datasets")
+    views = _check_channels(who, input_channels)
+    if int(batch_size) < 1:
+        raise ValueError(f"{who}: batch_size must be positive (got {batch_size})")
+    shard = _check_shard(who, shard)
+    samplers = [d.get("sampler") for d in datasets]
+    if not all(isinstance(s, GpuPatchSampler) for s in samplers):
+        raise ValueError(f"{who}: every dataset needs a GpuPatchSampler under 'sampler'")
+    s0 = samplers[0]
+    if s0.tile % 4 or s0.tile < 4:
+        raise ValueError(f"{who}: tile_size must be a multiple of 4 (got {s0.tile})")
+    if any(s.tile != s0.tile or s.device != s0.device for s in samplers):
+        raise ValueError(f"{who}: the samplers must share tile size and device")
+    if len({s.dsm_gt is None for s in samplers}) != 1:
+        raise ValueError(f"{who}: either every sampler or none has a ground-truth raster")
+    return datasets, samplers, views, shard
+
+
+def _dataset_pairs(who, d, s, di, input_channels, n_views):
+    """int32 [P, V] plane table of the image pairs of dataset di (an input with image views); V = n_views unless that is None."""
+    if s.orthos is None or not d.get("image_pairs"):
+        raise ValueError(f"{who}: input_channels={input_channels!r} needs orthos and image_pairs (dataset {di})")
+    pairs = np.array(_check_image_pairs(who, s, d["image_pairs"], f" (dataset {di})"), dtype=np.int32)
+    if n_views not in (None, pairs.shape[1]):
+        raise ValueError(f"{who}: the datasets must share the number of views per sample")
+    return pairs
+
+
+def _raster_desc(samplers, views, transform_orthos, with_gt):
+    """The rd_train_raster table of rd_assemble_train_patches, one row per sampler, as a numpy record array."""
+    desc = np.zeros(len(samplers), dtype=_RASTER_DESC)
+    for r, s in zip(desc, samplers):
+        r["dsm_in"], r["dsm_gt"] = s.dsm_in.data_ptr(), (s.dsm_gt.data_ptr() if with_gt else 0)
+        r["ortho"] = s.orthos.data_ptr() if views else 0
+        r["height"], r["width"], r["n_planes"] = s.h, s.w, (s.orthos.shape[0] if views else 0)
+        r["nodata"], r["dsm_std"], r["ortho_std"] = s.nodata, s.dsm_std, s.ortho_std
+        r["ortho_mode"], r["ortho_mean"] = _transform_mode(transform_orthos, s.ortho_mean)
+    return desc
+
+
+def _assemble_train(desc, n_rasters, tab, v, dsm_channel, t, with_gt, meta):
+    """One rd_assemble_train_patches launch on the current stream for the n samples of the device table `tab` (int32
+    [rows, n]) -> the batch dict of GpuTrainSet and GpuValSet: dsm_std / nodata are views of the table, `meta` holds the
+    caller's _META columns."""
+    n, dev = tab.shape[1], tab.device
+    inp = torch.empty(n, dsm_channel + v, t, t, dtype=torch.float32, device=dev)
+    mean = torch.empty(n, dtype=torch.float32, device=dev)
+    sums = torch.empty(n, 4, dtype=torch.float64, device=dev)
+    tgt = msk = None
+    if with_gt:
+        tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
+        msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
+    check(load().rd_assemble_train_patches(ptr(desc), n_rasters, ptr(tab), n, v, dsm_channel, t, ptr(inp), ptr(tgt),
+                                           ptr(msk), ptr(mean), ptr(sums), stream_ptr()), "assemble_train_patches")
+    batch = {"input": inp, "dsm_mean": mean, "dsm_std": tab[6].view(torch.float32), "nodata": tab[7].view(torch.float32), **meta}
+    if with_gt:
+        batch["target"], batch["loss_mask"] = tgt, msk.view(torch.bool)
+    return batch
 
 
 class TrainSampleSet:
@@ -433,39 +542,16 @@ class GpuTrainSet:
                  permute_images_within_pair: bool = False, augment: bool = True, transform_dsm: bool = True,
                  transform_orthos: bool = True, dsm_mean=None, shuffle: bool = True, generator=None, rng=None, shard=(0, 1),
                  prefetch: int = 1):
-        import numpy as np
-        if isinstance(datasets, dict):
-            datasets = [datasets]
-        if not datasets:
-            raise ValueError("GpuTrainSet: no datasets")
-        if input_channels not in ("geom",) + _VIEW_CHANNELS:
-            raise ValueError(f"GpuTrainSet: unknown input_channels {input_channels!r}")
-        if int(batch_size) < 1:
-            raise ValueError(f"GpuTrainSet: batch_size must be positive (got {batch_size})")
-        rank, world = int(shard[0]), int(shard[1])
-        if not 0 <= rank < world:
-            raise ValueError(f"GpuTrainSet: bad shard {shard!r}")
-        views = input_channels in _VIEW_CHANNELS
-        samplers = [d.get("sampler") for d in datasets]
-        if not all(isinstance(s, GpuPatchSampler) for s in samplers):
-            raise ValueError("GpuTrainSet: every dataset needs a GpuPatchSampler under 'sampler'")
+        datasets, samplers, views, (rank, world) = _check_loader_args("GpuTrainSet", datasets, input_channels, batch_size, shard)
         s0 = samplers[0]
         t = s0.tile
-        if t % 4 or t < 4:
-            raise ValueError(f"GpuTrainSet: tile_size must be a multiple of 4 (got {t})")
-        if any(s.tile != t or s.device != s0.device for s in samplers):
-            raise ValueError("GpuTrainSet: the samplers must share tile size and device")
-        if len({s.dsm_gt is None for s in samplers}) != 1:
-            raise ValueError("GpuTrainSet: either every sampler or none has a ground-truth raster")
         self.samplers, self.device, self.tile = samplers, s0.device, t
         self.has_gt = s0.dsm_gt is not None
         self.input_channels, self.batch_size, self.prefetch = input_channels, int(batch_size), int(prefetch)
         self.augment, self.permute, self.shuffle = bool(augment), bool(permute_images_within_pair), bool(shuffle)
         self.generator, self.shard = generator, (rank, world)
         self.dsm_channel = 0 if input_channels == "stereo" else 1
-        dsm_mode = 0 if not transform_dsm else (2 if not dsm_mean else 1)
-        f32bits = lambda v: int(np.array(v, dtype=np.float32).view(np.int32))       # noqa: E731
-        desc = np.zeros(len(datasets), dtype=_RASTER_DESC)
+        dsm_mode, dsm_mean = _transform_mode(transform_dsm, dsm_mean)
         ids, poss, pidx, cols, planes = [], [], [], [], []
         n_views = None
         for di, (d, s) in enumerate(zip(datasets, samplers)):
@@ -474,17 +560,8 @@ class GpuTrainSet:
                 if x0 < 0 or y0 < 0 or x1 >= s.w or y1 >= s.h:
                     raise ValueError(f"GpuTrainSet: area x {x0}..{x1}, y {y0}..{y1} of dataset {di} is not inside the "
                                      f"{s.h} x {s.w} raster")
-            pairs = None
             if views:
-                if s.orthos is None or not d.get("image_pairs"):
-                    raise ValueError(f"GpuTrainSet: input_channels={input_channels!r} needs orthos and image_pairs (dataset {di})")
-                pairs = np.array([[int(p) for p in pr] for pr in d["image_pairs"]], dtype=np.int32)
-                if pairs.ndim != 2 or pairs.shape[1] < 1:
-                    raise ValueError("GpuTrainSet: every image pair must have the same number of views")
-                if pairs.min() < 0 or pairs.max() >= s.orthos.shape[0]:
-                    raise ValueError(f"GpuTrainSet: an image index is outside the {s.orthos.shape[0]} ortho planes (dataset {di})")
-                if n_views not in (None, pairs.shape[1]):
-                    raise ValueError("GpuTrainSet: the datasets must share the number of views per sample")
+                pairs = _dataset_pairs("GpuTrainSet", d, s, di, input_channels, n_views)
                 n_views = pairs.shape[1]
             # the reference's draws, dataset after dataset (each DsmOrthoDataset constructor calls _determine_patches)
             pos, pi = tiling.draw_train_samples(area, t, d["n_samples"], input_channels, d.get("image_pairs"), use_all_stereo_pairs,
@@ -495,19 +572,12 @@ class GpuTrainSet:
             pidx.append(pi)
             c = np.zeros((_SAMPLE_INTS, m), dtype=np.int32)
             c[0], c[1], c[2], c[4] = di, pos[:, 0], pos[:, 1], dsm_mode
-            c[5] = f32bits(dsm_mean) if dsm_mode == 1 else 0
-            c[6], c[7] = f32bits(s.dsm_std), f32bits(s.nodata)          # the batch dict's per-sample dsm_std / nodata columns
+            c[5] = _f32bits(dsm_mean)                                   # 0.0 (all bits 0) unless the mode is 1
+            c[6], c[7] = _f32bits(s.dsm_std), _f32bits(s.nodata)        # the batch dict's per-sample dsm_std / nodata columns
             cols.append(c)
             if views:
                 planes.append(pairs[pi])
-            om = s.ortho_mean
-            r = desc[di]
-            r["dsm_in"], r["dsm_gt"] = s.dsm_in.data_ptr(), (s.dsm_gt.data_ptr() if self.has_gt else 0)
-            r["ortho"] = s.orthos.data_ptr() if views else 0
-            r["height"], r["width"], r["n_planes"] = s.h, s.w, (s.orthos.shape[0] if views else 0)
-            r["nodata"], r["dsm_std"], r["ortho_std"] = s.nodata, s.dsm_std, s.ortho_std
-            r["ortho_mode"] = 0 if not transform_orthos else (2 if not om else 1)
-            r["ortho_mean"] = float(om) if r["ortho_mode"] == 1 else 0.0
+        desc = _raster_desc(samplers, views, transform_orthos, self.has_gt)
         self.views = n_views or 0
         self._cols = np.concatenate(cols, axis=1)                                        # [8, m], static columns
         self._planes = np.concatenate(planes, axis=0) if views else np.zeros((self._cols.shape[1], 0), dtype=np.int32)
@@ -529,15 +599,13 @@ class GpuTrainSet:
     def table(self, index, aug=None, views=None):
         """Host sample table (int32 [8 + V, n], the column layout of rd_assemble_train_patches) for the samples `index` of the
         list; aug: int [n, 3] (k, flip_v, flip_h) or None; views: int [n, V] plane indices replacing the pairs' own order."""
-        import numpy as np
         idx = np.asarray(index, dtype=np.int64).reshape(-1)
         tab = np.empty((_SAMPLE_INTS + self.views, idx.size), dtype=np.int32)
         tab[:_SAMPLE_INTS] = self._cols[:, idx]
         if self.views:
             tab[_SAMPLE_INTS:] = (self._planes[idx] if views is None else np.asarray(views, dtype=np.int32).reshape(idx.size, -1)).T
         if aug is not None:
-            a = np.asarray(aug, dtype=np.int32).reshape(idx.size, 3)
-            tab[3] = a[:, 0] | (a[:, 1] << 2) | (a[:, 2] << 3)
+            tab[3] = _aug_code(np.asarray(aug), idx.size)
         return tab
 
     def assemble(self, index, aug=None, views=None):
@@ -546,34 +614,17 @@ class GpuTrainSet:
             return self._assemble(torch.from_numpy(self.table(index, aug, views)))
 
     def _assemble(self, tab_host):
-        dev, t, v = self.device, self.tile, self.views
         n = tab_host.shape[1]
-        tab = tab_host.to(dev, non_blocking=True)
-        c = self.dsm_channel + v
-        inp = torch.empty(n, c, t, t, dtype=torch.float32, device=dev)
-        mean = torch.empty(n, dtype=torch.float32, device=dev)
-        sums = torch.empty(n, 4, dtype=torch.float64, device=dev)
-        tgt = msk = None
-        if self.has_gt:
-            tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
-            msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
-        check(load().rd_assemble_train_patches(ptr(self._desc), len(self.samplers), ptr(tab), n, v, self.dsm_channel, t, ptr(inp),
-                                               ptr(tgt), ptr(msk), ptr(mean), ptr(sums), stream_ptr()), "assemble_train_patches")
+        tab = tab_host.to(self.device, non_blocking=True)
         nan = self._nan.get(n)
         if nan is None:
-            nan = self._nan[n] = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
-        batch = {"input": inp, "dsm_mean": mean, "dsm_std": tab[6].view(torch.float32), "nodata": tab[7].view(torch.float32),
-                 "patch_offset_y": tab[1].to(torch.int64), "patch_offset_x": tab[2].to(torch.int64),
-                 "patch_valid_pixels_uly": nan, "patch_valid_pixels_ulx": nan, "patch_valid_pixels_lry": nan,
-                 "patch_valid_pixels_lrx": nan}
-        if tgt is not None:
-            batch["target"], batch["loss_mask"] = tgt, msk.view(torch.bool)
-        return batch
+            nan = self._nan[n] = torch.full((n,), float("nan"), dtype=torch.float64, device=self.device)
+        meta = dict(zip(_META, (tab[1].to(torch.int64), tab[2].to(torch.int64), nan, nan, nan, nan)))
+        return _assemble_train(self._desc, len(self.samplers), tab, self.views, self.dsm_channel, self.tile, self.has_gt, meta)
 
     def epoch_tables(self):
         """One epoch's draws from `generator` -> [host sample table per batch] (pinned int32 [8 + V, n] each): the order
         (tiling.epoch_order), then the within-pair permutations, then k, flip_v, flip_h for every sample of the epoch."""
-        import numpy as np
         g = self.generator
         order = tiling.epoch_order(self._cols.shape[1], g, self.shard, self.shuffle).numpy()
         n_e, v = order.size, self.views
@@ -582,8 +633,7 @@ class GpuTrainSet:
             perm = torch.argsort(torch.rand(n_e, v, generator=g), dim=1).numpy()
             views = np.take_along_axis(self._planes[order], perm, axis=1)
         if self.augment:
-            aug = torch.stack([torch.randint(0, 4, (n_e,), generator=g), torch.randint(0, 2, (n_e,), generator=g),
-                               torch.randint(0, 2, (n_e,), generator=g)], 1).numpy()
+            aug = _draw_aug(n_e, g).numpy()
         tab = self.table(order, aug, views)
         rows = tab.shape[0]
         flat = torch.empty(max(tab.size, 1), dtype=torch.int32).pin_memory()
@@ -595,30 +645,7 @@ class GpuTrainSet:
         return out
 
     def __iter__(self):
-        tables = self.epoch_tables()
-        src = self.samplers[0]
-        with torch.cuda.device(self.device):
-            side = torch.cuda.Stream(device=self.device)
-        queue = []
-
-        def produce(tab_host):
-            with torch.cuda.device(self.device), torch.cuda.stream(side):
-                b = self._assemble(tab_host)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            return b, ev
-
-        for tab_host in tables:
-            queue.append(produce(tab_host))
-            if len(queue) > max(0, self.prefetch):
-                yield src._hand_over(queue.pop(0))
-        while queue:
-            yield src._hand_over(queue.pop(0))
-
-
-_TRAIN_AUG_BOX = 16                                 # RD_TRAIN_AUG_BOX
-_VAL_META = ("patch_offset_y", "patch_offset_x", "patch_valid_pixels_uly", "patch_valid_pixels_ulx", "patch_valid_pixels_lry",
-             "patch_valid_pixels_lrx")
+        yield from _prefetched(self.device, self.epoch_tables(), self._assemble, self.prefetch)
 
 
 class ValSampleSet:
@@ -657,44 +684,20 @@ class GpuValSet:
     def __init__(self, datasets, input_channels: str, batch_size: int, shard=(0, 1), prefetch: int = 1,
                  transform_dsm: bool = True, transform_orthos: bool = True, stride=None, augment: bool = False,
                  permute_images_within_pair: bool = False):
-        import numpy as np
         if augment:
             raise ValueError("GpuValSet: augment=True is not supported (the reference augments 'train' samples only)")
         if permute_images_within_pair:
             raise ValueError("GpuValSet: permute_images_within_pair=True is not supported")
-        if isinstance(datasets, dict):
-            datasets = [datasets]
-        if not datasets:
-            raise ValueError("GpuValSet: no datasets")
-        if input_channels not in ("geom",) + _VIEW_CHANNELS:
-            raise ValueError(f"GpuValSet: unknown input_channels {input_channels!r}")
-        if int(batch_size) < 1:
-            raise ValueError(f"GpuValSet: batch_size must be positive (got {batch_size})")
-        rank, world = int(shard[0]), int(shard[1])
-        if not 0 <= rank < world:
-            raise ValueError(f"GpuValSet: bad shard {shard!r}")
-        views = input_channels in _VIEW_CHANNELS
-        samplers = [d.get("sampler") for d in datasets]
-        if not all(isinstance(s, GpuPatchSampler) for s in samplers):
-            raise ValueError("GpuValSet: every dataset needs a GpuPatchSampler under 'sampler'")
+        datasets, samplers, views, self.shard = _check_loader_args("GpuValSet", datasets, input_channels, batch_size, shard)
         s0 = samplers[0]
         t = s0.tile
-        if t % 4 or t < 4:
-            raise ValueError(f"GpuValSet: tile_size must be a multiple of 4 (got {t})")
-        if any(s.tile != t or s.device != s0.device for s in samplers):
-            raise ValueError("GpuValSet: the samplers must share tile size and device")
-        if len({s.dsm_gt is None for s in samplers}) != 1:
-            raise ValueError("GpuValSet: either every sampler or none has a ground-truth raster")
         if s0.dsm_gt is None:
             raise ValueError("GpuValSet: a validation set needs the samplers' ground-truth rasters")
         if stride is not None and not 0 < int(stride) <= t:
             raise ValueError(f"GpuValSet: stride must be in 1..{t} (got {stride})")
         self.samplers, self.device, self.tile = samplers, s0.device, t
         self.input_channels, self.batch_size, self.prefetch = input_channels, int(batch_size), int(prefetch)
-        self.shard = (rank, world)
         self.dsm_channel = 0 if input_channels == "stereo" else 1
-        f32bits = lambda v: int(np.array(v, dtype=np.float32).view(np.int32))       # noqa: E731
-        desc = np.zeros(len(datasets), dtype=_RASTER_DESC)
         areas, pair_tabs = [], []
         n_views = None
         for di, (d, s) in enumerate(zip(datasets, samplers)):
@@ -708,27 +711,11 @@ class GpuValSet:
                                      f"tile inside the {s.h} x {s.w} raster")
             pairs = None
             if views:
-                if s.orthos is None or not d.get("image_pairs"):
-                    raise ValueError(f"GpuValSet: input_channels={input_channels!r} needs orthos and image_pairs (dataset {di})")
-                rows = [[int(p) for p in pr] for pr in d["image_pairs"]]
-                if len({len(r) for r in rows}) != 1 or not rows[0]:
-                    raise ValueError("GpuValSet: every image pair must have the same number of views")
-                pairs = np.array(rows, dtype=np.int32)
-                if pairs.min() < 0 or pairs.max() >= s.orthos.shape[0]:
-                    raise ValueError(f"GpuValSet: an image index is outside the {s.orthos.shape[0]} ortho planes (dataset {di})")
-                if n_views not in (None, pairs.shape[1]):
-                    raise ValueError("GpuValSet: the datasets must share the number of views per sample")
+                pairs = _dataset_pairs("GpuValSet", d, s, di, input_channels, n_views)
                 n_views = pairs.shape[1]
             areas.append((xe, ye, len(pairs) if views else 1))
             pair_tabs.append(pairs)
-            om = s.ortho_mean
-            r = desc[di]
-            r["dsm_in"], r["dsm_gt"] = s.dsm_in.data_ptr(), s.dsm_gt.data_ptr()
-            r["ortho"] = s.orthos.data_ptr() if views else 0
-            r["height"], r["width"], r["n_planes"] = s.h, s.w, (s.orthos.shape[0] if views else 0)
-            r["nodata"], r["dsm_std"], r["ortho_std"] = s.nodata, s.dsm_std, s.ortho_std
-            r["ortho_mode"] = 0 if not transform_orthos else (2 if not om else 1)
-            r["ortho_mean"] = float(om) if r["ortho_mode"] == 1 else 0.0
+        desc = _raster_desc(samplers, views, transform_orthos, True)
         self.views = v = n_views or 0
         used_stride, ids, pos, reg, pidx = tiling.concat_val_samples(areas, t, stride, views)
         ids, pidx = np.array(ids, dtype=np.int64), np.array(pidx, dtype=np.int64)
@@ -740,11 +727,10 @@ class GpuValSet:
         cols[0], cols[1], cols[2], cols[3] = ids, pos[:, 0], pos[:, 1], _TRAIN_AUG_BOX
         for di, (d, s) in enumerate(zip(datasets, samplers)):
             sel = ids == di
-            mean = d.get("dsm_mean")
-            mode = 0 if not transform_dsm else (2 if not mean else 1)
+            mode, mean = _transform_mode(transform_dsm, d.get("dsm_mean"))
             cols[4, sel] = mode
-            cols[5, sel] = f32bits(mean) if mode == 1 else 0
-            cols[6, sel], cols[7, sel] = f32bits(s.dsm_std), f32bits(s.nodata)
+            cols[5, sel] = _f32bits(mean)                               # 0.0 (all bits 0) unless the mode is 1
+            cols[6, sel], cols[7, sel] = _f32bits(s.dsm_std), _f32bits(s.nodata)
             if views:
                 cols[_SAMPLE_INTS:_SAMPLE_INTS + v, sel] = pair_tabs[di][pidx[sel]].T
         cols[_SAMPLE_INTS + v:] = reg.T
@@ -761,7 +747,7 @@ class GpuValSet:
         with torch.cuda.device(self.device):
             self._desc = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(self.device)
             self._table = torch.from_numpy(flat).to(self.device)
-            self._meta = {k: torch.from_numpy(np.ascontiguousarray(meta[:, c])).to(self.device) for c, k in enumerate(_VAL_META)}
+            self._meta = {k: torch.from_numpy(np.ascontiguousarray(meta[:, c])).to(self.device) for c, k in enumerate(_META)}
 
     def __len__(self):
         return len(self._bounds)
@@ -778,42 +764,12 @@ class GpuValSet:
             return self._assemble(int(k))
 
     def _assemble(self, k):
-        dev, t, v = self.device, self.tile, self.views
         if not 0 <= k < len(self._bounds):
             raise ValueError(f"GpuValSet: batch {k} outside 0..{len(self._bounds) - 1}")
         j0, j1 = int(self._first[k]), int(self._first[k + 1])
-        n = j1 - j0
-        tab = self._table[j0 * self._rows:j1 * self._rows].view(self._rows, n)
-        inp = torch.empty(n, self.dsm_channel + v, t, t, dtype=torch.float32, device=dev)
-        mean = torch.empty(n, dtype=torch.float32, device=dev)
-        sums = torch.empty(n, 4, dtype=torch.float64, device=dev)
-        tgt = torch.empty(n, 1, t, t, dtype=torch.float32, device=dev)
-        msk = torch.empty(n, 1, t, t, dtype=torch.uint8, device=dev)
-        check(load().rd_assemble_train_patches(ptr(self._desc), len(self.samplers), tab.data_ptr(), n, v, self.dsm_channel, t,
-                                               ptr(inp), ptr(tgt), ptr(msk), ptr(mean), ptr(sums), stream_ptr()),
-              "assemble_train_patches")
-        batch = {"input": inp, "dsm_mean": mean, "dsm_std": tab[6].view(torch.float32), "nodata": tab[7].view(torch.float32)}
-        for key, col in self._meta.items():
-            batch[key] = col[j0:j1]
-        batch["target"], batch["loss_mask"] = tgt, msk.view(torch.bool)
-        return batch
+        tab = self._table[j0 * self._rows:j1 * self._rows].view(self._rows, j1 - j0)
+        meta = {key: col[j0:j1] for key, col in self._meta.items()}
+        return _assemble_train(self._desc, len(self.samplers), tab, self.views, self.dsm_channel, self.tile, True, meta)
 
     def __iter__(self):
-        src = self.samplers[0]
-        with torch.cuda.device(self.device):
-            side = torch.cuda.Stream(device=self.device)
-        queue = []
-
-        def produce(k):
-            with torch.cuda.device(self.device), torch.cuda.stream(side):
-                b = self._assemble(k)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            return b, ev
-
-        for k in range(len(self._bounds)):
-            queue.append(produce(k))
-            if len(queue) > max(0, self.prefetch):
-                yield src._hand_over(queue.pop(0))
-        while queue:
-            yield src._hand_over(queue.pop(0))
+        yield from _prefetched(self.device, range(len(self._bounds)), self._assemble, self.prefetch)

@@ -168,6 +168,12 @@ SIGNATURES_PAIRS = {
     "rd_blend_accumulate_planes": (I, [P, P, P, P, P, P, P, I, I, I, I, P, I, LL, I, I, P]),
     "rd_fuse_planes": (I, [P, LL, I, LL, I, P, I, P, P]),
 }
+# include/resdepth_hip_eval.h (scoring the planes of a pair sweep), one to one as above
+SIGNATURES_EVAL = {
+    "rd_eval_classify_planes": (I, [P, LL, I, P, P, I, P, I, P, P, P, P, P, P, I, I, I, D, P, P, P, P, P, P]),
+    "rd_residual_stats_pooled_ws_bytes": (SZ, [LL, I]),
+    "rd_residual_stats_pooled": (I, [P, LL, I, I, I, P, P, LL, P, P, I, P, P, SZ, P]),
+}
 
 
 class ProfEntry(C.Structure):
@@ -188,7 +194,8 @@ def load():
                 f"resdepth_amd: HIP library not built ({LIB_PATH} missing). Run resdepth_amd/csrc/build.sh; "
                 "there is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
+                + list(SIGNATURES_EVAL.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

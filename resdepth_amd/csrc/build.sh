@@ -26,7 +26,8 @@ pids=()
 for f in rd_runtime rd_igemm rd_convt rd_wgrad_strip rd_elementwise rd_edge_conv rd_stats rd_trainset; do
   if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ "$HERE/rd_common.h" -nt "$OBJ/$f.o" ] \
      || [ "$HERE/rd_mfma_dev.h" -nt "$OBJ/$f.o" ] || [ "$HERE/rd_nt.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/resdepth_hip.h" -nt "$OBJ/$f.o" ] \
-     || [ "$HERE/../../include/resdepth_hip_tta.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/resdepth_hip_pairs.h" -nt "$OBJ/$f.o" ]; then
+     || [ "$HERE/../../include/resdepth_hip_tta.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/resdepth_hip_pairs.h" -nt "$OBJ/$f.o" ] \
+     || [ "$HERE/../../include/resdepth_hip_eval.h" -nt "$OBJ/$f.o" ]; then
     F="$FLAGS"; [ $f = rd_wgrad_strip ] && F="$BASE"     # 144 accumulator registers: AGPR-form MFMA (see the file header)
     $HIPCC $F -c "$HERE/$f.hip" -o "$OBJ/$f.o" &
     pids+=($!)

@@ -23,10 +23,14 @@ from .trainer import DevicePrefetcher
 class PairSweep:
     """What predict_pairs_linear_blend returns: `fused` np.float64 [rows, cols]; `spread` [rows, cols] or None; `pairs`
     np.float64 [P, rows, cols] (plane p = the sweep of image_pairs[p]) or None; `image_pairs`.  The arrays are views of pinned
-    host memory the object keeps alive (`host`: with host="reuse" the next call of the same shape overwrites them)."""
+    host memory the object keeps alive (`host`: with host="reuse" the next call of the same shape overwrites them).
+    `device_pairs` / `device_fused`: None, or with keep_device=True the device tensors the sweep produced."""
 
-    def __init__(self, fused, spread, pairs, image_pairs, host):
+    def __init__(self, fused, spread, pairs, image_pairs, host, device_pairs=None, device_fused=None):
         self.fused, self.spread, self.pairs, self.image_pairs, self.host = fused, spread, pairs, image_pairs, host
+        # with keep_device=True: the sweep's own device tensors ([P, rows, cols] and [rows, cols] fp64), not copies --
+        # evaluation.evaluate_pairs_statistics scores them where they are
+        self.device_pairs, self.device_fused = device_pairs, device_fused
 
 
 class _PairHost:
@@ -40,11 +44,14 @@ class _PairHost:
 _host_cache = {}
 
 
-def predict_pairs_linear_blend(dataloader, model, fuse: str = "median", spread=None, return_pairs: bool = True, host=None):
+def predict_pairs_linear_blend(dataloader, model, fuse: str = "median", spread=None, return_pairs: bool = True, host=None,
+                               keep_device: bool = False):
     """One sweep over a loader that carries the "pair" column (GpuGridTiles(..., sweep_pairs=True)) -> PairSweep.
     fuse: "mean" | "median"; spread: None | "range" | "std" (ops.fuse_planes); return_pairs=False leaves the P planes on the
     device and returns only the fused surface (and the spread): 8 or 16 bytes per raster pixel cross to the host instead of
-    8 (P + 1) or 8 (P + 2).  host: None = fresh pinned arrays per call; "reuse" = one cached block per (planes, rows, cols)."""
+    8 (P + 1) or 8 (P + 2).  host: None = fresh pinned arrays per call; "reuse" = one cached block per (planes, rows, cols).
+    keep_device=True: the PairSweep also carries the device tensors `device_pairs` [P, rows, cols] and `device_fused` (what the
+    sweep holds, no copy) for evaluation.evaluate_pairs_statistics; the host results are the same either way."""
     if not torch.cuda.is_available():
         raise RuntimeError("resdepth_amd.predict_pairs_linear_blend runs on a HIP device only (no CPU fallback)")
     if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
@@ -103,4 +110,4 @@ def predict_pairs_linear_blend(dataloader, model, fuse: str = "median", spread=N
         torch.cuda.current_stream(device).synchronize()
     out = host.t.numpy()
     return PairSweep(out[0], out[1] if want_spread else None, out[1 + int(want_spread):] if return_pairs else None,
-                     getattr(ds, "image_pairs", None), host)
+                     getattr(ds, "image_pairs", None), host, raster if keep_device else None, fused if keep_device else None)

@@ -174,15 +174,9 @@ def _float_raster(x, dev):
     return t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float64)
 
 
-def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
-              nodata, dev):
-    """-> (stats {'before', 'after'}, r_after, cls, classes) with r_after / cls on the device."""
-    pred = _on(prediction, dev, torch.float64)
-    init, g = _float_raster(initial, dev), _float_raster(gt, dev)
-    if pred.dim() != 2 or pred.shape != init.shape or pred.shape != g.shape:
-        raise ValueError(f"evaluate: prediction {tuple(pred.shape)}, initial {tuple(init.shape)} and ground truth "
-                         f"{tuple(g.shape)} must be equal 2-D rasters")
-    rows, cols = pred.shape
+def _eval_inputs(rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev):
+    """What a classification pass needs besides the DSMs: the uint8 device masks (building already dilated), the classes
+    they define, the area rectangles as a ctypes array and the nodata value."""
     gm = None if mask_gt is None else _mask_pair(mask_gt, dev)[0]
     bdil = bnod = water = forest = None
     classes = ["all"]
@@ -202,6 +196,20 @@ def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_w
     rects = _rects(area_defn, rows, cols)
     rect_a = None if rects is None else (ctypes.c_int * (4 * max(len(rects), 1)))(*[v for r in rects for v in r])
     nd = float("nan") if nodata is None else float(nodata)
+    return gm, bdil, bnod, water, forest, classes, rect_a, (-1 if rects is None else len(rects)), nd
+
+
+def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
+              nodata, dev):
+    """-> (stats {'before', 'after'}, r_after, cls, classes) with r_after / cls on the device."""
+    pred = _on(prediction, dev, torch.float64)
+    init, g = _float_raster(initial, dev), _float_raster(gt, dev)
+    if pred.dim() != 2 or pred.shape != init.shape or pred.shape != g.shape:
+        raise ValueError(f"evaluate: prediction {tuple(pred.shape)}, initial {tuple(init.shape)} and ground truth "
+                         f"{tuple(g.shape)} must be equal 2-D rasters")
+    rows, cols = pred.shape
+    gm, bdil, bnod, water, forest, classes, rect_a, n_rects, nd = _eval_inputs(
+        rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev)
     r_before = torch.empty((rows, cols), dtype=torch.float64, device=dev)
     r_after = torch.empty_like(r_before)
     cls = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
@@ -209,8 +217,8 @@ def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_w
     with torch.cuda.device(dev):
         check(lib.rd_eval_classify(ptr(pred), ptr(init), int(init.dtype == torch.float64), ptr(g),
                                    int(g.dtype == torch.float64), ptr(gm), ptr(bdil), ptr(bnod), ptr(water), ptr(forest),
-                                   rect_a, -1 if rects is None else len(rects), rows, cols, nd, ptr(r_before),
-                                   ptr(r_after), ptr(cls), stream_ptr()), "eval_classify")
+                                   rect_a, n_rects, rows, cols, nd, ptr(r_before), ptr(r_after), ptr(cls), stream_ptr()),
+              "eval_classify")
     sets = []
     for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)):
         for c in classes:
@@ -302,37 +310,34 @@ _HEADINGS = {"all": "OVERALL", "building": "BUILDING PIXELS", "terrain": "TERRAI
              "terrain_nowater_noforest": ("TERRAIN PIXELS WITHOUT WATER/FOREST", "TERRAIN PIXELS WITHOUT FOREST")}
 
 
-def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logger_root, area_defn=None,
-                         path_gt_mask=None, path_building_mask=None, path_water_mask=None, path_forest_mask=None,
-                         logger_stats=None, residual_threshold=None, *, nodata=None, gsd=None, device="cuda"):
-    """Drop-in for lib/evaluation.py:163 evaluate_performance: the same report on `logger_stats` and the same return
-    value, the attribute dict `residuals.after` of host np.ma.MaskedArrays (class -> residuals of the refined DSM).
+def _default_stats_logger(name="stats_logger"):
+    logger_stats = logging.getLogger(name)
+    logger_stats.setLevel(logging.INFO)
+    if not logger_stats.handlers:
+        logger_stats.addHandler(logging.StreamHandler())
+    return logger_stats
 
-    The DSMs are arrays / tensors or dataset-like objects (GetRasterBand(1).ReadAsArray(), GetNoDataValue(),
-    GetGeoTransform()); for arrays the ground truth's nodata value and the GSD come from `nodata=` / `gsd=`.  Mask
-    arguments: arrays (value 1 = set), (values, nodata) tuples, dataset-like objects or paths (paths need osgeo.gdal; a
-    path that does not exist is logged and skipped; a missing ground-truth mask means all ground-truth pixels)."""
-    if logger_stats is None:
-        logger_stats = logging.getLogger("stats_logger")
-        logger_stats.setLevel(logging.INFO)
-        if not logger_stats.handlers:
-            logger_stats.addHandler(logging.StreamHandler())
 
-    def raster(x, what):
-        if isinstance(x, str):
-            logger_root.info("\tLoad the {}...".format(what))
-            x = _open(x)
-        return (x.GetRasterBand(1).ReadAsArray(), x) if hasattr(x, "GetRasterBand") else (x, None)
+def _raster_arg(x, what, logger_root):
+    """A DSM argument -> (array, dataset or None): paths are opened, datasets read."""
+    if isinstance(x, str):
+        logger_root.info("\tLoad the {}...".format(what))
+        x = _open(x)
+    return (x.GetRasterBand(1).ReadAsArray(), x) if hasattr(x, "GetRasterBand") else (x, None)
 
-    pred, _ = raster(raster_prediction, "refined DSM")
-    gt, ds_gt = raster(ds_raster_gt, "ground truth DSM")
-    init, ds_in = raster(ds_raster_input, "initial DSM")
+
+def _performance_inputs(ds_raster_input, ds_raster_gt, logger_root, path_gt_mask, path_building_mask, path_water_mask,
+                        path_forest_mask, nodata, gsd, who):
+    """The arguments evaluate_performance shares with evaluate_pairs_performance, resolved in the reference's order
+    -> (gt, init, nodata, gsd, mask_gt, mask_building, mask_water, mask_forest)."""
+    gt, ds_gt = _raster_arg(ds_raster_gt, "ground truth DSM", logger_root)
+    init, ds_in = _raster_arg(ds_raster_input, "initial DSM", logger_root)
     if ds_gt is not None:
         nodata = ds_gt.GetRasterBand(1).GetNoDataValue()
     if ds_in is not None:
         gsd = ds_in.GetGeoTransform()[1]
     if gsd is None:
-        raise ValueError("evaluate_performance: pass gsd= when the initial DSM is an array")
+        raise ValueError("{}: pass gsd= when the initial DSM is an array".format(who))
 
     mask_gt = _mask_arg(path_gt_mask, "ground truth mask", logger_root)
     if mask_gt is False:
@@ -353,12 +358,18 @@ def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logge
         if mask_f is False:
             logger_root.info("Evaluating the performance without excluding forest pixels.")
             mask_f = None
+    return gt, init, nodata, gsd, mask_gt, mask_b, mask_w, mask_f
 
-    dev = _device(device)
-    logger_root.info("\tCompute residual errors and statistics before and after the refinement...")
-    stats, r_after, cls, classes = _evaluate(pred, init, gt, area_defn, mask_gt, mask_b, mask_w, mask_f,
-                                             residual_threshold, nodata, dev)
 
+def _heading(c, classes):
+    head = _HEADINGS[c]
+    if isinstance(head, tuple):
+        head = head[0] if "terrain_nowater" in classes else head[1]
+    return head
+
+
+def _write_report(stats, classes, gsd, residual_threshold, logger_stats):
+    """The report of lib/evaluation.py:361-449 on `logger_stats` from stats.before / stats.after."""
     area_size = float(stats.before.all["count_total"] * gsd * gsd) / 1000000
     logger_stats.info("\n\nPerformance Evaluation\n----------------------\n")
     logger_stats.info("Number of pixels:\t\t\t{}".format(int(stats.before.all["count_total"])))
@@ -366,14 +377,36 @@ def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logge
     if residual_threshold:
         logger_stats.info("Truncation threshold:\t\t\t{:.2f} m\n".format(residual_threshold))
     for c in classes:
-        head = _HEADINGS[c]
-        if isinstance(head, tuple):
-            head = head[0] if "terrain_nowater" in classes else head[1]
+        head = _heading(c, classes)
         for when, dsm in (("before", "INITIAL"), ("after", "REFINED")):
             title = "STATISTICS, {}: {} DSM".format(head, dsm)
             rule = len(title) + (c == "all" and when == "before")     # the reference's first rule is one dash longer
             logger_stats.info("\n{}\n{}\n".format(title, "-" * rule))
             print_statistics(stats[when][c], logger_stats)
+
+
+def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logger_root, area_defn=None,
+                         path_gt_mask=None, path_building_mask=None, path_water_mask=None, path_forest_mask=None,
+                         logger_stats=None, residual_threshold=None, *, nodata=None, gsd=None, device="cuda"):
+    """Drop-in for lib/evaluation.py:163 evaluate_performance: the same report on `logger_stats` and the same return
+    value, the attribute dict `residuals.after` of host np.ma.MaskedArrays (class -> residuals of the refined DSM).
+
+    The DSMs are arrays / tensors or dataset-like objects (GetRasterBand(1).ReadAsArray(), GetNoDataValue(),
+    GetGeoTransform()); for arrays the ground truth's nodata value and the GSD come from `nodata=` / `gsd=`.  Mask
+    arguments: arrays (value 1 = set), (values, nodata) tuples, dataset-like objects or paths (paths need osgeo.gdal; a
+    path that does not exist is logged and skipped; a missing ground-truth mask means all ground-truth pixels)."""
+    if logger_stats is None:
+        logger_stats = _default_stats_logger()
+    pred, _ = _raster_arg(raster_prediction, "refined DSM", logger_root)
+    gt, init, nodata, gsd, mask_gt, mask_b, mask_w, mask_f = _performance_inputs(
+        ds_raster_input, ds_raster_gt, logger_root, path_gt_mask, path_building_mask, path_water_mask, path_forest_mask,
+        nodata, gsd, "evaluate_performance")
+
+    dev = _device(device)
+    logger_root.info("\tCompute residual errors and statistics before and after the refinement...")
+    stats, r_after, cls, classes = _evaluate(pred, init, gt, area_defn, mask_gt, mask_b, mask_w, mask_f,
+                                             residual_threshold, nodata, dev)
+    _write_report(stats, classes, gsd, residual_threshold, logger_stats)
 
     data = r_after.cpu().numpy()
     bits = cls.cpu().numpy()
@@ -404,3 +437,160 @@ def get_statistics_masked(residuals_masked, residual_threshold=None, device="cud
     sets = [(0, 1, None)] + ([(0, 1, residual_threshold)] if residual_threshold else [])
     res = _run_sets(r, None, valid, sets, dev)
     return _stats_dict(res[0], res[1] if residual_threshold else None, residual_threshold)
+
+
+# ---- every pair plane of a sweep, and the pool of all pairs (test.py:191-357) ----------------------------------------------
+VALID_EXTRA = 64                                      # RD_CLS_VALID_EXTRA (include/resdepth_hip_eval.h)
+MAX_PLANES = 16                                       # RD_EVAL_MAX_PLANES
+
+
+def _queue_pooled(res, n_planes, p0, p1, cls, valid, sets, out, dev):
+    """rd_residual_stats_pooled of planes p0 .. p1 - 1 of `res` [P, rows, cols] into out [len(sets), 8] (device), enqueued
+    only.  sets: [(need bits, threshold or None)]."""
+    n, ns = cls.numel(), len(sets)
+    lib = load()
+    need_a = (ctypes.c_int * ns)(*[b for b, _ in sets])
+    thr_a = (ctypes.c_double * ns)(*[float(t) if t else -1.0 for _, t in sets])
+    ws = workspace(lib.rd_residual_stats_pooled_ws_bytes(n, ns), dev, slot=3)
+    check(lib.rd_residual_stats_pooled(ptr(res), n, n_planes, p0, p1, ptr(cls), ptr(valid), n, need_a, thr_a, ns, ptr(out),
+                                       ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats_pooled")
+
+
+def _class_stats(rows, classes, thr):
+    """rows [len(classes) * (2 if thr else 1), 8] in class order (full, truncated) -> {class: stats}."""
+    step = 2 if thr else 1
+    return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr)) for q, c in enumerate(classes))
+
+
+def _is_sweep(x):
+    return hasattr(x, "image_pairs") and hasattr(x, "pairs") and hasattr(x, "fused")
+
+
+def _private_f64(x, dev):
+    """-> (contiguous fp64 tensor on dev, whether it is a buffer of this call that may be overwritten)."""
+    t = _on(x, dev, torch.float64)
+    return t, not (torch.is_tensor(x) and t.data_ptr() == x.data_ptr())
+
+
+def _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
+                    fused, nodata, device):
+    """-> (stats {'before', 'pairs', 'pooled'[, 'fused']}, classes)"""
+    if _is_sweep(pairs):
+        sweep, pairs = pairs, getattr(pairs, "device_pairs", None)
+        if pairs is None:
+            pairs = sweep.pairs
+        if pairs is None:
+            raise ValueError("evaluate_pairs: the PairSweep holds no planes (predict_pairs_linear_blend(..., "
+                             "return_pairs=False) without keep_device=True)")
+        if fused is None:
+            fused = getattr(sweep, "device_fused", None)
+            fused = sweep.fused if fused is None else fused
+    dev = None
+    for x in (pairs, fused, initial, gt):
+        if torch.is_tensor(x) and x.is_cuda:
+            dev = x.device
+            break
+    dev = _device(dev if dev is not None else device)
+    if len(pairs.shape) != 3:
+        raise ValueError(f"evaluate_pairs: pairs must be [P, rows, cols] (got shape {tuple(pairs.shape)})")
+    n_planes = int(pairs.shape[0])
+    if not 1 <= n_planes <= MAX_PLANES:
+        raise ValueError(f"evaluate_pairs: {n_planes} planes (1..{MAX_PLANES})")
+    init, g = _float_raster(initial, dev), _float_raster(gt, dev)
+    if tuple(pairs.shape[1:]) != tuple(init.shape) or init.dim() != 2 or init.shape != g.shape:
+        raise ValueError(f"evaluate: pair planes {tuple(pairs.shape[1:])}, initial {tuple(init.shape)} and ground truth "
+                         f"{tuple(g.shape)} must be equal 2-D rasters")
+    if fused is not None and tuple(fused.shape) != tuple(init.shape):
+        raise ValueError(f"evaluate: fused surface {tuple(fused.shape)} != raster shape {tuple(init.shape)}")
+    rows, cols = init.shape
+    gm, bdil, bnod, water, forest, classes, rect_a, n_rects, nd = _eval_inputs(
+        rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev)
+    # host planes are uploaded once into a buffer of this call and turned into residuals in place; a device tensor of the
+    # caller is read where it is and the residuals go to a buffer of their own
+    planes, own = _private_f64(pairs, dev)
+    res = planes if own else torch.empty_like(planes)
+    fz = r_fused = None
+    if fused is not None:
+        fz, own = _private_f64(fused, dev)
+        r_fused = fz if own else torch.empty_like(fz)
+    r_before = torch.empty((rows, cols), dtype=torch.float64, device=dev)
+    cls = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    valid = torch.empty((rows, cols), dtype=torch.int16, device=dev)
+    thr = residual_threshold
+    lib = load()
+    with torch.cuda.device(dev):
+        check(lib.rd_eval_classify_planes(ptr(planes), rows * cols, n_planes, ptr(fz), ptr(init),
+                                          int(init.dtype == torch.float64), ptr(g), int(g.dtype == torch.float64), ptr(gm),
+                                          ptr(bdil), ptr(bnod), ptr(water), ptr(forest), rect_a, n_rects, rows, cols, nd,
+                                          ptr(r_before), ptr(res), ptr(r_fused), ptr(cls), ptr(valid), stream_ptr()),
+              "eval_classify_planes")
+        psets = [(CLASS_BITS[c], t) for c in classes for t in ((None, thr) if thr else (None,))]
+        out = torch.empty((n_planes + 1, len(psets), 8), dtype=torch.float64, device=dev)
+        for p in range(n_planes):
+            _queue_pooled(res, n_planes, p, p + 1, cls, valid, psets, out[p], dev)
+        _queue_pooled(res, n_planes, 0, n_planes, cls, valid, psets, out[n_planes], dev)
+    # the initial DSM and the fused surface: two sources of the existing sets kernel, off the same class byte
+    sets = [(0, VALID_BEFORE | b, t) for b, t in psets]
+    if fz is not None:
+        sets += [(1, VALID_EXTRA | b, t) for b, t in psets]
+    single = _run_sets(r_before, r_fused, cls, sets, dev)
+    rows_out = out.cpu().numpy()
+    stats = AttrDict(before=_class_stats(single[:len(psets)], classes, thr),
+                     pairs=[_class_stats(rows_out[p], classes, thr) for p in range(n_planes)],
+                     pooled=_class_stats(rows_out[n_planes], classes, thr))
+    if fz is not None:
+        stats.fused = _class_stats(single[len(psets):], classes, thr)
+    return stats, classes
+
+
+def evaluate_pairs_statistics(pairs, initial, gt, area_defn=None, mask_gt=None, mask_building=None, mask_water=None,
+                              mask_forest=None, residual_threshold=None, *, fused=None, nodata=None, device="cuda"):
+    """The statistics of test.py:191-357 for the P predictions of a pair sweep, scored where the sweep left them: ONE
+    dilation and ONE classification pass whatever P is (rd_eval_classify_planes), then every pair's statistics sets and the
+    sets of the pool of all pairs' residuals (rd_residual_stats_pooled), and the initial DSM and the fused surface from the
+    same class byte (rd_residual_stats_sets).
+
+    pairs: [P, rows, cols] array / tensor (1 <= P <= 16), or the PairSweep of predict_pairs_linear_blend -- its device planes
+    are used when it carries them (keep_device=True), and its fused surface when `fused` is not given.  Device tensors are
+    scored in place of residence and never written; host arrays are uploaded once.  Everything else as evaluate_statistics.
+    -> {'before': {class: stats}, 'pairs': [P x {class: stats}], 'pooled': {class: stats}[, 'fused': {class: stats}]}, every
+    stats dict in the reference's get_statistics format (attribute access)."""
+    return _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest,
+                           residual_threshold, fused, nodata, device)[0]
+
+
+def evaluate_pairs_performance(pairs, ds_raster_input, ds_raster_gt, logger_root, area_defn=None, path_gt_mask=None,
+                               path_building_mask=None, path_water_mask=None, path_forest_mask=None, loggers_stats=None,
+                               logger_stats_pooled=None, residual_threshold=None, *, fused=None, nodata=None, gsd=None,
+                               device="cuda"):
+    """Drop-in for the evaluation of test.py:191-357: on loggers_stats[p] the report evaluate_performance writes for
+    prediction p, and on logger_stats_pooled the "statistics over all predictions" block (test.py:326-357; written when
+    there is more than one pair, as in the reference, or when the logger is given).  pairs / fused as
+    evaluate_pairs_statistics, every other argument as evaluate_performance.  -> the statistics object of
+    evaluate_pairs_statistics; the residual rasters are not returned (evaluate_performance per plane gives them)."""
+    gt, init, nodata, gsd, mask_gt, mask_b, mask_w, mask_f = _performance_inputs(
+        ds_raster_input, ds_raster_gt, logger_root, path_gt_mask, path_building_mask, path_water_mask, path_forest_mask,
+        nodata, gsd, "evaluate_pairs_performance")
+    logger_root.info("\tCompute residual errors and statistics before and after the refinement...")
+    stats, classes = _evaluate_pairs(pairs, init, gt, area_defn, mask_gt, mask_b, mask_w, mask_f, residual_threshold,
+                                     fused, nodata, device)
+    n_planes = len(stats.pairs)
+    if loggers_stats is None:
+        loggers_stats = [_default_stats_logger()] * n_planes
+    if len(loggers_stats) != n_planes:
+        raise ValueError(f"evaluate_pairs_performance: {len(loggers_stats)} loggers for {n_planes} pairs")
+    for p, logger_stats in enumerate(loggers_stats):
+        _write_report(AttrDict(before=stats.before, after=stats.pairs[p]), classes, gsd, residual_threshold, logger_stats)
+    if logger_stats_pooled is None and n_planes > 1:
+        logger_stats_pooled = _default_stats_logger("stats_logger_overall")
+    if logger_stats_pooled is not None:
+        logger_root.info("\nCompute residual errors averaged over all predictions...")
+        title = "Performance Evaluation: Statistics over all predictions"
+        logger_stats_pooled.info("\n{}\n{}\n".format(title, "-" * len(title)))
+        if residual_threshold:
+            logger_stats_pooled.info("Truncation threshold:\t\t\t{:.2f} m\n".format(residual_threshold))
+        for c in classes:
+            title = "STATISTICS, {}: REFINED DSM".format(_heading(c, classes))
+            logger_stats_pooled.info("\n{}\n{}\n".format(title, "-" * len(title)))
+            print_statistics(stats.pooled[c], logger_stats_pooled)
+    return stats

@@ -203,20 +203,35 @@ int rd_residual_stats(const double* raster, const float* gt, const uint8_t* mask
 
 }  // extern "C"
 
-// ---- class-partitioned evaluation (lib/evaluation.py:163-457 evaluate_performance) -----------------------------------
+// ---- class-partitioned evaluation (lib/evaluation.py:163-457 evaluate_performance; for the P planes of a pair sweep
+// test.py:191-357, include/resdepth_hip_eval.h) ----------------------------------------------------------------------------
 // rd_dilate_mask: the L1-ball dilation of lib/rasterutils.py:88 in one launch.  A 64 x 32 output tile is staged in LDS
 // with a k-pixel halo; per haloed row and output column the distance to the nearest set pixel of that row (capped at
 // k + 1), then out = OR over dy of (row distance at dy) <= k - |dy|, exactly the diamond of radius k.
 //
-// rd_residual_stats_sets: every set's moments in one pass (per-set registers, fixed-order block partials), then the
-// exact medians of all sets by the radix select of rd_residual_stats with the histograms of up to SEL_GROUP selectors
-// (set x {median, absolute median} in one phase, NMAD in the next) filled by one read of the residuals per pass.
+// Classification, two forms of one pixel rule.  Shared (area_contains, gt_valid, class_bits): the area rectangles, the
+// ground truth's validity and the building / terrain bits, worked out once per pixel.  eval_classify_kernel adds one
+// prediction with its residual and RD_CLS_VALID_AFTER.  eval_classify_planes_kernel adds P planes and an optional extra
+// surface (the fused one): per plane one load, one subtraction, one store and one bit of the validity word.  The planes are
+// walked with a running pointer, one value live at a time: no array of P values, so nothing is indexed by a runtime number
+// (scripts/check_isa.sh fails the build on scratch).  The residual planes may be the input planes: a thread reads plane p
+// of its pixel before it writes it and no other thread touches that element, so neither pointer is __restrict__.
+//
+// Statistics sets, two forms of one engine.  Shared: every set's moments in one pass (SetMoments: per-set registers,
+// fixed-order block partials), then the exact medians of all sets by the radix select of rd_residual_stats with the
+// histograms of up to SEL_GROUP selectors (set x {median, absolute median} in one phase, NMAD in the next) filled by one
+// read of the values per pass (hist_begin / hist_count / hist_flush); the finish, shift, pick and select-finish kernels, the
+// workspace (StatsWs) and the launch schedule (make_select_plan, run_selection).  A form is the loop that produces
+// (class, value): rd_residual_stats_sets reads two sources and a set picks one; rd_residual_stats_pooled draws a set's
+// members from planes p0 .. p1 - 1 of one strided source under a per-pixel validity word.  There the class byte and the
+// validity word are read once per round and serve every plane and every selector; the plane loop is the outer one, so a
+// round holds HB values of ONE plane in registers (indexed by the unrolled u only).
 
 namespace rd {
 
 constexpr int DIL_TW = 64, DIL_TH = 32;
 constexpr int SEL_GROUP = 20;        // selectors sharing one histogram pass: 20 x 2 ranks x 256 bins x 4 B = 40 KB of LDS
-constexpr int HB = 8;                // pixels per thread and round of the histogram kernel
+constexpr int HB = 8;                // pixels per thread and round of the histogram kernels
 
 __global__ __launch_bounds__(256) void dilate_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int rows,
                                                      int cols, int k) {
@@ -258,6 +273,33 @@ __device__ __forceinline__ double load_f(const void* p, int f64, long i) {
     return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i];
 }
 
+__device__ __forceinline__ bool area_contains(const EvalRects& area, int y, int x) {
+    bool in = area.n < 0;
+    for (int q = 0; q < area.n; ++q)
+        in |= y >= area.r[q][0] && y < area.r[q][1] && x >= area.r[q][2] && x < area.r[q][3];
+    return in;
+}
+
+__device__ __forceinline__ bool gt_valid(bool in, double g, double nodata, const uint8_t* gt_mask, long i) {
+    return in && g != nodata && (!gt_mask || gt_mask[i]);
+}
+
+// the building / terrain bits of pixel i (none without a building mask)
+__device__ __forceinline__ unsigned class_bits(bool in, long i, const uint8_t* bdil, const uint8_t* bnod,
+                                               const uint8_t* water, const uint8_t* forest) {
+    unsigned c = 0;
+    if (bdil) {
+        const bool b = bdil[i] != 0;
+        const bool t = in && !b && !(bnod && bnod[i]);
+        const bool tw = t && !(water && water[i]);
+        if (in && b) c |= RD_CLS_BUILDING;
+        if (t) c |= RD_CLS_TERRAIN;
+        if (tw) c |= RD_CLS_TERRAIN_NOWATER;
+        if (tw && !(forest && forest[i])) c |= RD_CLS_TERRAIN_NOWATER_NOFOREST;
+    }
+    return c;
+}
+
 __global__ __launch_bounds__(256) void eval_classify_kernel(
     const double* __restrict__ pred, const void* __restrict__ init, int init_f64, const void* __restrict__ gt, int gt_f64,
     const uint8_t* __restrict__ gt_mask, const uint8_t* __restrict__ bdil, const uint8_t* __restrict__ bnod,
@@ -267,26 +309,51 @@ __global__ __launch_bounds__(256) void eval_classify_kernel(
     if (x >= cols) return;
     for (int y = blockIdx.y; y < rows; y += gridDim.y) {
         const long i = (long)y * cols + x;
-        bool in = area.n < 0;
-        for (int q = 0; q < area.n; ++q)
-            in |= y >= area.r[q][0] && y < area.r[q][1] && x >= area.r[q][2] && x < area.r[q][3];
+        const bool in = area_contains(area, y, x);
         const double g = load_f(gt, gt_f64, i), a = load_f(init, init_f64, i), p = pred[i];
-        const bool gok = in && g != nodata && (!gt_mask || gt_mask[i]);
+        const bool gok = gt_valid(in, g, nodata, gt_mask, i);
         unsigned c = 0;
         if (gok && a != nodata) c |= RD_CLS_VALID_BEFORE;
         if (gok && p != nodata) c |= RD_CLS_VALID_AFTER;
-        if (bdil) {
-            const bool b = bdil[i] != 0;
-            const bool t = in && !b && !(bnod && bnod[i]);
-            const bool tw = t && !(water && water[i]);
-            if (in && b) c |= RD_CLS_BUILDING;
-            if (t) c |= RD_CLS_TERRAIN;
-            if (tw) c |= RD_CLS_TERRAIN_NOWATER;
-            if (tw && !(forest && forest[i])) c |= RD_CLS_TERRAIN_NOWATER_NOFOREST;
-        }
+        c |= class_bits(in, i, bdil, bnod, water, forest);
         rb[i] = a - g;
         ra[i] = p - g;
         cls[i] = (uint8_t)c;
+    }
+}
+
+__global__ __launch_bounds__(256) void eval_classify_planes_kernel(
+    const double* planes, long plane_stride, int n_planes, const double* extra, const void* __restrict__ init, int init_f64,
+    const void* __restrict__ gt, int gt_f64, const uint8_t* __restrict__ gt_mask, const uint8_t* __restrict__ bdil,
+    const uint8_t* __restrict__ bnod, const uint8_t* __restrict__ water, const uint8_t* __restrict__ forest, EvalRects area,
+    int rows, int cols, double nodata, double* __restrict__ rb, double* res, double* r_extra, uint8_t* __restrict__ cls,
+    uint16_t* __restrict__ valid) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= cols) return;
+    for (int y = blockIdx.y; y < rows; y += gridDim.y) {
+        const long i = (long)y * cols + x;
+        const bool in = area_contains(area, y, x);
+        const double g = load_f(gt, gt_f64, i), a = load_f(init, init_f64, i);
+        const bool gok = gt_valid(in, g, nodata, gt_mask, i);
+        unsigned c = 0;
+        if (gok && a != nodata) c |= RD_CLS_VALID_BEFORE;
+        c |= class_bits(in, i, bdil, bnod, water, forest);
+        if (extra) {
+            const double e = extra[i];
+            if (gok && e != nodata) c |= RD_CLS_VALID_EXTRA;
+            r_extra[i] = e - g;
+        }
+        unsigned v = 0;
+        const double* src = planes + i;
+        double* dst = res + i;
+        for (int p = 0; p < n_planes; ++p, src += plane_stride, dst += plane_stride) {
+            const double pv = *src;
+            if (gok && pv != nodata) v |= 1u << p;
+            *dst = pv - g;
+        }
+        if (rb) rb[i] = a - g;
+        cls[i] = (uint8_t)c;
+        valid[i] = (uint16_t)v;
     }
 }
 
@@ -314,24 +381,27 @@ __device__ __forceinline__ double wave_max(double v) {
     return v;
 }
 
-// partial[(block * n_sets + s) * 5 + q]: count, sum|r|, sum r^2, min, max of set s over the block's pixels
-__global__ __launch_bounds__(256) void sets_moments_kernel(const double* __restrict__ src0, const double* __restrict__ src1,
-                                                           const uint8_t* __restrict__ cls, long n, SetSpecs sp,
-                                                           double* __restrict__ partial) {
+// count, sum|r|, sum r^2, min, max of every set over a thread's values, in registers: the arrays are indexed by unrolled
+// loops only (an array indexed by a runtime value goes to scratch)
+struct SetMoments {
     double cnt[RD_STATS_MAX_SETS], sa[RD_STATS_MAX_SETS], sq[RD_STATS_MAX_SETS], mn[RD_STATS_MAX_SETS],
         mx[RD_STATS_MAX_SETS];
-#pragma unroll
-    for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
-        cnt[s] = sa[s] = sq[s] = 0.0;
-        mn[s] = INFINITY;
-        mx[s] = -INFINITY;
-    }
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const double r0 = src0[i], r1 = src1[i];
-        const unsigned c = cls[i];
+
+    __device__ __forceinline__ SetMoments() {
 #pragma unroll
         for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
-            const double d = sp.src[s] ? r1 : r0;
+            cnt[s] = sa[s] = sq[s] = 0.0;
+            mn[s] = INFINITY;
+            mx[s] = -INFINITY;
+        }
+    }
+
+    // one pixel (or pixel-plane) of class c: value_of(s) is what set s reads there
+    template <class ValueOf>
+    __device__ __forceinline__ void add(const SetSpecs& sp, unsigned c, ValueOf value_of) {
+#pragma unroll
+        for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
+            const double d = value_of(s);
             if (s < sp.n && in_set(sp, s, c, d)) {
                 cnt[s] += 1.0;
                 sa[s] += fabs(d);
@@ -341,27 +411,62 @@ __global__ __launch_bounds__(256) void sets_moments_kernel(const double* __restr
             }
         }
     }
-    __shared__ double red[4][5];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+
+    // partial[(block * n_sets + s) * 5 + q]: the block's moments of set s, waves added in a fixed order
+    __device__ __forceinline__ void store(double* __restrict__ partial, const SetSpecs& sp, double (*red)[5]) const {
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-    for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
-        if (s >= sp.n) continue;
-        const double v0 = wave_sum(cnt[s]), v1 = wave_sum(sa[s]), v2 = wave_sum(sq[s]), v3 = wave_min(mn[s]),
-                     v4 = wave_max(mx[s]);
-        if (lane == 0) {
-            red[w][0] = v0; red[w][1] = v1; red[w][2] = v2; red[w][3] = v3; red[w][4] = v4;
+        for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
+            if (s >= sp.n) continue;
+            const double v0 = wave_sum(cnt[s]), v1 = wave_sum(sa[s]), v2 = wave_sum(sq[s]), v3 = wave_min(mn[s]),
+                         v4 = wave_max(mx[s]);
+            if (lane == 0) {
+                red[w][0] = v0; red[w][1] = v1; red[w][2] = v2; red[w][3] = v3; red[w][4] = v4;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double* o = partial + ((long)blockIdx.x * sp.n + s) * 5;
+                o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+                o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+                o[2] = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+                o[3] = fmin(fmin(red[0][3], red[1][3]), fmin(red[2][3], red[3][3]));
+                o[4] = fmax(fmax(red[0][4], red[1][4]), fmax(red[2][4], red[3][4]));
+            }
+            __syncthreads();
         }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double* o = partial + ((long)blockIdx.x * sp.n + s) * 5;
-            o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-            o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-            o[2] = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-            o[3] = fmin(fmin(red[0][3], red[1][3]), fmin(red[2][3], red[3][3]));
-            o[4] = fmax(fmax(red[0][4], red[1][4]), fmax(red[2][4], red[3][4]));
-        }
-        __syncthreads();
     }
+};
+
+__global__ __launch_bounds__(256) void sets_moments_kernel(const double* __restrict__ src0, const double* __restrict__ src1,
+                                                           const uint8_t* __restrict__ cls, long n, SetSpecs sp,
+                                                           double* __restrict__ partial) {
+    __shared__ double red[4][5];
+    SetMoments m;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const double r0 = src0[i], r1 = src1[i];
+        m.add(sp, cls[i], [&](int s) { return sp.src[s] ? r1 : r0; });      // a set reads one of two sources
+    }
+    m.store(partial, sp, red);
+}
+
+// a thread adds its pixels in pixel order and, per pixel, the planes p0 .. p1 - 1 in plane order
+__global__ __launch_bounds__(256) void pooled_moments_kernel(const double* __restrict__ src, long plane_stride, int p0, int p1,
+                                                             const uint8_t* __restrict__ cls,
+                                                             const uint16_t* __restrict__ valid, long n, SetSpecs sp,
+                                                             double* __restrict__ partial) {
+    __shared__ double red[4][5];
+    SetMoments m;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const unsigned c = cls[i];
+        const unsigned v = valid ? (unsigned)valid[i] : 0xffffu;
+        const double* q = src + (long)p0 * plane_stride + i;
+        for (int p = p0; p < p1; ++p, q += plane_stride) {
+            if (!((v >> p) & 1u)) continue;
+            const double d = *q;
+            m.add(sp, c, [&](int) { return d; });                           // every set reads the one value
+        }
+    }
+    m.store(partial, sp, red);
 }
 
 // one block per set: fixed-order sum of the block partials (strided per thread, then a fixed tree) -> out[s*8 + 0..4];
@@ -424,15 +529,11 @@ struct SelGroup {
     int mode[SEL_GROUP];
 };
 
-// hist[j*512 + side*256 + bin]: the pass's byte histogram of selector j's values under each of its two prefixes; while the
-// two prefixes agree both ranks read side 0 (the values are counted once)
-__global__ __launch_bounds__(512) void sets_hist_kernel(const double* __restrict__ src0, const double* __restrict__ src1,
-                                                        const uint8_t* __restrict__ cls, long n, SetSpecs sp, SelGroup g,
-                                                        int pass, const SelState* __restrict__ st,
-                                                        unsigned* __restrict__ hist) {
-    __shared__ unsigned lh[SEL_GROUP * 512];
-    __shared__ unsigned long long pf[SEL_GROUP][2];
-    __shared__ double sh[SEL_GROUP];
+// The histogram kernels.  hist[j*512 + side*256 + bin]: the pass's byte histogram of selector j's values under each of its two
+// prefixes; while the two prefixes agree both ranks read side 0 (the values are counted once).  A kernel holds HB pixels per
+// thread in registers per round, so the selector parameters are read once per round, not per pixel.
+__device__ __forceinline__ void hist_begin(unsigned* lh, unsigned long long (*pf)[2], double* sh, const SelGroup& g,
+                                           const SelState* __restrict__ st) {
     for (int i = threadIdx.x; i < g.n * 512; i += blockDim.x) lh[i] = 0u;
     if (threadIdx.x < g.n) {
         const SelState& t = st[g.set[threadIdx.x] * 3 + g.mode[threadIdx.x]];
@@ -441,8 +542,39 @@ __global__ __launch_bounds__(512) void sets_hist_kernel(const double* __restrict
         sh[threadIdx.x] = t.shift;
     }
     __syncthreads();
+}
+
+// one selector's histogram h over HB values r[] of class c[] (-1: no value there)
+__device__ __forceinline__ void hist_count(unsigned* h, const double (&r)[HB], const int (&c)[HB], int need, double thr,
+                                           int mode, double shift, unsigned long long p0, unsigned long long p1, int pass) {
     const int hs = 8 * (pass + 1);
-    // HB pixels per thread in registers per round: the selector parameters are read once per round, not per pixel
+#pragma unroll
+    for (int u = 0; u < HB; ++u) {
+        if (c[u] < 0 || (c[u] & need) != need || (thr > 0.0 && !(fabs(r[u]) <= thr))) continue;
+        const unsigned long long k = key_of(pick_value(r[u], mode, shift));
+        const unsigned long long hi = pass == 7 ? 0ull : (k >> hs);
+        const unsigned b = (unsigned)((k >> (8 * pass)) & 255ull);
+        if (hi == p0)
+            atomicAdd(&h[b], 1u);
+        else if (hi == p1)
+            atomicAdd(&h[256 + b], 1u);
+    }
+}
+
+__device__ __forceinline__ void hist_flush(const unsigned* lh, const SelGroup& g, unsigned* __restrict__ hist) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < g.n * 512; i += blockDim.x)
+        if (lh[i]) atomicAdd(&hist[i], lh[i]);
+}
+
+__global__ __launch_bounds__(512) void sets_hist_kernel(const double* __restrict__ src0, const double* __restrict__ src1,
+                                                        const uint8_t* __restrict__ cls, long n, SetSpecs sp, SelGroup g,
+                                                        int pass, const SelState* __restrict__ st,
+                                                        unsigned* __restrict__ hist) {
+    __shared__ unsigned lh[SEL_GROUP * 512];
+    __shared__ unsigned long long pf[SEL_GROUP][2];
+    __shared__ double sh[SEL_GROUP];
+    hist_begin(lh, pf, sh, g, st);
     const long step = (long)gridDim.x * blockDim.x * HB;
     for (long base = (long)blockIdx.x * blockDim.x * HB + threadIdx.x; base < n; base += step) {
         double r0[HB], r1[HB];
@@ -456,28 +588,55 @@ __global__ __launch_bounds__(512) void sets_hist_kernel(const double* __restrict
             c[u] = ok ? (int)cls[i] : -1;
         }
         for (int j = 0; j < g.n; ++j) {
-            const int s = g.set[j], mode = g.mode[j], src = sp.src[s];
-            const int need = (int)sp.need[s];
-            const double thr = sp.thr[s], shift = sh[j];
-            const unsigned long long p0 = pf[j][0], p1 = pf[j][1];
-            unsigned* h = lh + j * 512;
+            const int s = g.set[j], src = sp.src[s];
+            double r[HB];
+#pragma unroll
+            for (int u = 0; u < HB; ++u) r[u] = src ? r1[u] : r0[u];
+            hist_count(lh + j * 512, r, c, (int)sp.need[s], sp.thr[s], g.mode[j], sh[j], pf[j][0], pf[j][1], pass);
+        }
+    }
+    hist_flush(lh, g, hist);
+}
+
+// per round the class bytes and validity words of HB pixels are read once; per plane the HB values, and the class with the
+// plane's validity folded in (-1 = skip)
+__global__ __launch_bounds__(512) void pooled_hist_kernel(const double* __restrict__ src, long plane_stride, int p0, int p1,
+                                                          const uint8_t* __restrict__ cls, const uint16_t* __restrict__ valid,
+                                                          long n, SetSpecs sp, SelGroup g, int pass,
+                                                          const SelState* __restrict__ st, unsigned* __restrict__ hist) {
+    __shared__ unsigned lh[SEL_GROUP * 512];
+    __shared__ unsigned long long pf[SEL_GROUP][2];
+    __shared__ double sh[SEL_GROUP];
+    hist_begin(lh, pf, sh, g, st);
+    const long step = (long)gridDim.x * blockDim.x * HB;
+    for (long base = (long)blockIdx.x * blockDim.x * HB + threadIdx.x; base < n; base += step) {
+        int c0[HB];
+        unsigned v[HB];
+#pragma unroll
+        for (int u = 0; u < HB; ++u) {
+            const long i = base + (long)u * blockDim.x;
+            const bool ok = i < n;
+            c0[u] = ok ? (int)cls[i] : -1;
+            v[u] = ok ? (valid ? (unsigned)valid[i] : 0xffffu) : 0u;
+        }
+        const double* q = src + (long)p0 * plane_stride;
+        for (int p = p0; p < p1; ++p, q += plane_stride) {
+            double r[HB];
+            int c[HB];
 #pragma unroll
             for (int u = 0; u < HB; ++u) {
-                const double r = src ? r1[u] : r0[u];
-                if (c[u] < 0 || (c[u] & need) != need || (thr > 0.0 && !(fabs(r) <= thr))) continue;
-                const unsigned long long k = key_of(pick_value(r, mode, shift));
-                const unsigned long long hi = pass == 7 ? 0ull : (k >> hs);
-                const unsigned b = (unsigned)((k >> (8 * pass)) & 255ull);
-                if (hi == p0)
-                    atomicAdd(&h[b], 1u);
-                else if (hi == p1)
-                    atomicAdd(&h[256 + b], 1u);
+                const long i = base + (long)u * blockDim.x;
+                const bool ok = c0[u] >= 0 && ((v[u] >> p) & 1u);
+                r[u] = ok ? q[i] : 0.0;
+                c[u] = ok ? c0[u] : -1;
+            }
+            for (int j = 0; j < g.n; ++j) {
+                const int s = g.set[j];
+                hist_count(lh + j * 512, r, c, (int)sp.need[s], sp.thr[s], g.mode[j], sh[j], pf[j][0], pf[j][1], pass);
             }
         }
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < g.n * 512; i += blockDim.x)
-        if (lh[i]) atomicAdd(&hist[i], lh[i]);
+    hist_flush(lh, g, hist);
 }
 
 // one block per selector: the bin holding each rank (block-wide inclusive scan), prefixes and ranks advance, the
@@ -537,6 +696,24 @@ __global__ void sets_zero_kernel(unsigned* __restrict__ p, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
 }
 
+// ---- host side of the two forms ----
+static void fill_rects(EvalRects& area, const int* rects, int n_rects) {
+    area.n = n_rects;
+    for (int q = 0; q < n_rects; ++q)
+        for (int e = 0; e < 4; ++e) area.r[q][e] = rects[q * 4 + e];
+}
+static dim3 classify_grid(int rows, int cols) { return dim3((cols + 255) / 256, rows < 65535 ? rows : 65535); }
+
+// set_src == nullptr: every set reads source 0
+static void fill_specs(SetSpecs& sp, int n_sets, const int* set_src, const int* set_need, const double* set_thr) {
+    sp.n = n_sets;
+    for (int i = 0; i < RD_STATS_MAX_SETS; ++i) {
+        sp.src[i] = i < n_sets && set_src ? set_src[i] : 0;
+        sp.need[i] = i < n_sets ? (unsigned)set_need[i] : 0u;
+        sp.thr[i] = i < n_sets ? set_thr[i] : -1.0;
+    }
+}
+
 static int sets_moment_blocks(long n) {
     long g = (n + 255) / 256;
     return (int)(g > 1024 ? 1024 : (g < 1 ? 1 : g));
@@ -544,6 +721,59 @@ static int sets_moment_blocks(long n) {
 static int sets_hist_blocks(long n) {
     long g = (n + 512 * HB - 1) / (512 * HB);
     return (int)(g > 1024 ? 1024 : (g < 1 ? 1 : g));
+}
+
+// the workspace of a statistics call: block partials | selection states | histograms
+struct StatsWs {
+    double* partial;
+    SelState* st;
+    unsigned* hist;
+};
+// -> the bytes a call over n values needs; with w, the layout carved from ws
+static size_t stats_ws_layout(long n, void* ws = nullptr, StatsWs* w = nullptr) {
+    const size_t o_st = (size_t)sets_moment_blocks(n) * RD_STATS_MAX_SETS * 5 * sizeof(double);
+    const size_t o_hist = o_st + (size_t)RD_STATS_MAX_SETS * 3 * sizeof(SelState);
+    if (w) *w = StatsWs{(double*)ws, (SelState*)((char*)ws + o_st), (unsigned*)((char*)ws + o_hist)};
+    return o_hist + (size_t)SEL_GROUP * 512 * sizeof(unsigned) + 256;
+}
+
+// selectors: every set's median and absolute median (phase 0), then every set's NMAD (phase 1), SEL_GROUP per pass
+struct SelectPlan {
+    SelGroup groups[3 * RD_STATS_MAX_SETS / SEL_GROUP + 3];
+    int phase_end[2], ng;
+};
+static SelectPlan make_select_plan(int n_sets) {
+    SelectPlan plan;
+    plan.ng = 0;
+    for (int phase = 0; phase < 2; ++phase) {
+        const int nsel = phase == 0 ? 2 * n_sets : n_sets;
+        for (int j0 = 0; j0 < nsel; j0 += SEL_GROUP) {
+            SelGroup& g = plan.groups[plan.ng++];
+            g.n = nsel - j0 < SEL_GROUP ? nsel - j0 : SEL_GROUP;
+            for (int j = 0; j < SEL_GROUP; ++j) {
+                const int q = j0 + (j < g.n ? j : 0);
+                g.set[j] = phase == 0 ? q >> 1 : q;
+                g.mode[j] = phase == 0 ? (q & 1) : 2;
+            }
+        }
+        plan.phase_end[phase] = plan.ng;
+    }
+    return plan;
+}
+
+// per group: [the NMAD shifts before the first group of phase 1,] 8 x (launch_hist(group, pass), pick), select-finish
+template <class LaunchHist>
+static void run_selection(hipStream_t s, const SelectPlan& plan, int n_sets, double* out, SelState* st, unsigned* hist,
+                          LaunchHist launch_hist) {
+    for (int gi = 0; gi < plan.ng; ++gi) {
+        const SelGroup& g = plan.groups[gi];
+        if (gi == plan.phase_end[0]) RD_LAUNCH(sets_shift_kernel, dim3(1), dim3(64), 0, s, (const double*)out, n_sets, st);
+        for (int pass = 7; pass >= 0; --pass) {
+            launch_hist(g, pass);
+            RD_LAUNCH(sets_pick_kernel, dim3(g.n), dim3(256), 0, s, g, st, hist);
+        }
+        RD_LAUNCH(sets_select_finish_kernel, dim3(1), dim3(64), 0, s, g, (const SelState*)st, out);
+    }
 }
 
 }  // namespace rd
@@ -571,23 +801,46 @@ int rd_eval_classify(const double* prediction, const void* initial, int initial_
     RD_REQUIRE(n_rects <= RD_EVAL_MAX_RECTS && (n_rects <= 0 || rects), "rd_eval_classify: %d area rectangles (at most %d)",
                n_rects, RD_EVAL_MAX_RECTS);
     EvalRects area;
-    area.n = n_rects;
-    for (int q = 0; q < n_rects; ++q)
-        for (int e = 0; e < 4; ++e) area.r[q][e] = rects[q * 4 + e];
+    fill_rects(area, rects, n_rects);
     hipStream_t s = (hipStream_t)s_;
     const double n = (double)rows * cols;
     ProfScope ps(s, "eval_classify", 0, n * (8.0 + (initial_f64 ? 8 : 4) + (gt_f64 ? 8 : 4) + 16.0 + 1.0));
-    const dim3 grid((cols + 255) / 256, rows < 65535 ? rows : 65535);
-    RD_LAUNCH(eval_classify_kernel, grid, dim3(256), 0, s, prediction, initial, initial_f64 ? 1 : 0, gt, gt_f64 ? 1 : 0,
-              gt_mask, building, building_nodata, water, forest, area, rows, cols, nodata, r_before, r_after, cls);
+    RD_LAUNCH(eval_classify_kernel, classify_grid(rows, cols), dim3(256), 0, s, prediction, initial, initial_f64 ? 1 : 0, gt,
+              gt_f64 ? 1 : 0, gt_mask, building, building_nodata, water, forest, area, rows, cols, nodata, r_before, r_after,
+              cls);
     RD_LAUNCH_CHECK("eval_classify");
     return RD_OK;
 }
 
-size_t rd_residual_stats_sets_ws_bytes(long long n, int n_sets) {
-    return (size_t)sets_moment_blocks(n) * RD_STATS_MAX_SETS * 5 * sizeof(double) +
-           (size_t)RD_STATS_MAX_SETS * 3 * sizeof(SelState) + (size_t)SEL_GROUP * 512 * sizeof(unsigned) + 256;
+int rd_eval_classify_planes(const double* planes, long long plane_stride, int n_planes, const double* extra,
+                            const void* initial, int initial_f64, const void* gt, int gt_f64, const uint8_t* gt_mask,
+                            const uint8_t* building, const uint8_t* building_nodata, const uint8_t* water,
+                            const uint8_t* forest, const int* rects, int n_rects, int rows, int cols, double nodata,
+                            double* r_before, double* residuals, double* r_extra, uint8_t* cls, uint16_t* valid,
+                            rd_stream_t s_) {
+    RD_REQUIRE(planes && initial && gt && residuals && cls && valid && rows > 0 && cols > 0,
+               "rd_eval_classify_planes: bad arguments");
+    RD_REQUIRE(n_planes >= 1 && n_planes <= RD_EVAL_MAX_PLANES, "rd_eval_classify_planes: n_planes must be in 1..%d (got %d)",
+               RD_EVAL_MAX_PLANES, n_planes);
+    RD_REQUIRE(plane_stride >= (long long)rows * cols, "rd_eval_classify_planes: plane_stride %lld < rows * cols = %lld",
+               plane_stride, (long long)rows * cols);
+    RD_REQUIRE(!extra == !r_extra, "rd_eval_classify_planes: extra and r_extra come together");
+    RD_REQUIRE(n_rects <= RD_EVAL_MAX_RECTS && (n_rects <= 0 || rects),
+               "rd_eval_classify_planes: %d area rectangles (at most %d)", n_rects, RD_EVAL_MAX_RECTS);
+    EvalRects area;
+    fill_rects(area, rects, n_rects);
+    hipStream_t s = (hipStream_t)s_;
+    const double n = (double)rows * cols;
+    ProfScope ps(s, "eval_classify_planes", 0,
+                 n * (16.0 * (n_planes + (extra ? 1 : 0)) + (initial_f64 ? 8 : 4) + (gt_f64 ? 8 : 4) + (r_before ? 8.0 : 0.0) + 3.0));
+    RD_LAUNCH(eval_classify_planes_kernel, classify_grid(rows, cols), dim3(256), 0, s, planes, (long)plane_stride, n_planes,
+              extra, initial, initial_f64 ? 1 : 0, gt, gt_f64 ? 1 : 0, gt_mask, building, building_nodata, water, forest, area,
+              rows, cols, nodata, r_before, residuals, r_extra, cls, valid);
+    RD_LAUNCH_CHECK("eval_classify_planes");
+    return RD_OK;
 }
+
+size_t rd_residual_stats_sets_ws_bytes(long long n, int n_sets) { return stats_ws_layout(n); }
 
 int rd_residual_stats_sets(const double* src0, const double* src1, const uint8_t* cls, long long n, const int* set_src,
                            const int* set_need, const double* set_thr, int n_sets, double* out, void* ws,
@@ -601,51 +854,73 @@ int rd_residual_stats_sets(const double* src0, const double* src1, const uint8_t
         return RD_ERR_WS;
     }
     SetSpecs sp;
-    sp.n = n_sets;
-    for (int i = 0; i < RD_STATS_MAX_SETS; ++i) {
-        sp.src[i] = i < n_sets ? set_src[i] : 0;
-        sp.need[i] = i < n_sets ? (unsigned)set_need[i] : 0u;
-        sp.thr[i] = i < n_sets ? set_thr[i] : -1.0;
+    fill_specs(sp, n_sets, set_src, set_need, set_thr);
+    for (int i = 0; i < n_sets; ++i)
         RD_REQUIRE(sp.src[i] == 0 || (sp.src[i] == 1 && src1), "rd_residual_stats_sets: set %d reads source %d", i,
                    sp.src[i]);
-    }
     if (!src1) src1 = src0;
     hipStream_t s = (hipStream_t)s_;
     const int nbm = sets_moment_blocks(n), nbh = sets_hist_blocks(n);
-    char* base = (char*)ws;
-    double* partial = (double*)base;
-    SelState* st = (SelState*)(base + (size_t)nbm * RD_STATS_MAX_SETS * 5 * sizeof(double));
-    unsigned* hist = (unsigned*)((char*)st + (size_t)RD_STATS_MAX_SETS * 3 * sizeof(SelState));
-    // selectors: every set's median and absolute median (phase 0), then every set's NMAD (phase 1), SEL_GROUP per pass
-    SelGroup groups[3 * RD_STATS_MAX_SETS / SEL_GROUP + 3];
-    int phase_end[2] = {0, 0}, ng = 0;
-    for (int phase = 0; phase < 2; ++phase) {
-        const int nsel = phase == 0 ? 2 * n_sets : n_sets;
-        for (int j0 = 0; j0 < nsel; j0 += SEL_GROUP) {
-            SelGroup& g = groups[ng++];
-            g.n = nsel - j0 < SEL_GROUP ? nsel - j0 : SEL_GROUP;
-            for (int j = 0; j < SEL_GROUP; ++j) {
-                const int q = j0 + (j < g.n ? j : 0);
-                g.set[j] = phase == 0 ? q >> 1 : q;
-                g.mode[j] = phase == 0 ? (q & 1) : 2;
-            }
-        }
-        phase_end[phase] = ng;
-    }
-    ProfScope ps(s, "residual_stats_sets", 0, 17.0 * n * (1 + 8 * ng));
-    RD_LAUNCH(sets_zero_kernel, dim3(1), dim3(256), 0, s, hist, SEL_GROUP * 512);
-    RD_LAUNCH(sets_moments_kernel, dim3(nbm), dim3(256), 0, s, src0, src1, cls, (long)n, sp, partial);
-    RD_LAUNCH(sets_moments_finish_kernel, dim3(n_sets), dim3(256), 0, s, (const double*)partial, nbm, n_sets, out, st);
-    for (int gi = 0; gi < ng; ++gi) {
-        if (gi == phase_end[0]) RD_LAUNCH(sets_shift_kernel, dim3(1), dim3(64), 0, s, (const double*)out, n_sets, st);
-        for (int pass = 7; pass >= 0; --pass) {
-            RD_LAUNCH(sets_hist_kernel, dim3(nbh), dim3(512), 0, s, src0, src1, cls, (long)n, sp, groups[gi], pass,
-                      (const SelState*)st, hist);
-            RD_LAUNCH(sets_pick_kernel, dim3(groups[gi].n), dim3(256), 0, s, groups[gi], st, hist);
-        }
-        RD_LAUNCH(sets_select_finish_kernel, dim3(1), dim3(64), 0, s, groups[gi], (const SelState*)st, out);
-    }
+    StatsWs w;
+    stats_ws_layout(n, ws, &w);
+    const SelectPlan plan = make_select_plan(n_sets);
+    ProfScope ps(s, "residual_stats_sets", 0, 17.0 * n * (1 + 8 * plan.ng));
+    RD_LAUNCH(sets_zero_kernel, dim3(1), dim3(256), 0, s, w.hist, SEL_GROUP * 512);
+    RD_LAUNCH(sets_moments_kernel, dim3(nbm), dim3(256), 0, s, src0, src1, cls, (long)n, sp, w.partial);
+    RD_LAUNCH(sets_moments_finish_kernel, dim3(n_sets), dim3(256), 0, s, (const double*)w.partial, nbm, n_sets, out, w.st);
+    run_selection(s, plan, n_sets, out, w.st, w.hist, [&](const SelGroup& g, int pass) {
+        RD_LAUNCH(sets_hist_kernel, dim3(nbh), dim3(512), 0, s, src0, src1, cls, (long)n, sp, g, pass, (const SelState*)w.st,
+                  w.hist);
+    });
     RD_LAUNCH_CHECK("residual_stats_sets");
+    return RD_OK;
+}
+
+size_t rd_residual_stats_pooled_ws_bytes(long long n, int n_sets) { return rd_residual_stats_sets_ws_bytes(n, n_sets); }
+
+int rd_residual_stats_pooled(const double* src, long long plane_stride, int n_planes, int p0, int p1, const uint8_t* cls,
+                             const uint16_t* valid, long long n, const int* set_need, const double* set_thr, int n_sets,
+                             double* out, void* ws, size_t ws_bytes, rd_stream_t s_) {
+    RD_REQUIRE(src && cls && out && n > 0 && set_need && set_thr, "rd_residual_stats_pooled: bad arguments");
+    RD_REQUIRE(n_planes >= 1 && n_planes <= RD_EVAL_MAX_PLANES, "rd_residual_stats_pooled: n_planes must be in 1..%d (got %d)",
+               RD_EVAL_MAX_PLANES, n_planes);
+    RD_REQUIRE(p0 >= 0 && p0 < p1 && p1 <= n_planes, "rd_residual_stats_pooled: planes [%d, %d) outside the %d planes", p0, p1,
+               n_planes);
+    RD_REQUIRE(plane_stride >= n, "rd_residual_stats_pooled: plane_stride %lld < n = %lld", plane_stride, n);
+    RD_REQUIRE(n_sets >= 1 && n_sets <= RD_STATS_MAX_SETS, "rd_residual_stats_pooled: %d sets (1..%d)", n_sets,
+               RD_STATS_MAX_SETS);
+    // the histograms are 32-bit counters: a bin may hold every member of a set
+    RD_REQUIRE(n < (1ll << 32) && (long long)(p1 - p0) * n < (1ll << 32),
+               "rd_residual_stats_pooled: (p1 - p0) * n = %d * %lld values reach 2^32 (32-bit histogram counters)", p1 - p0, n);
+    if (!ws || ws_bytes < rd_residual_stats_pooled_ws_bytes(n, n_sets)) {
+        set_error("rd_residual_stats_pooled: workspace too small (%zu < %zu)", ws_bytes,
+                  rd_residual_stats_pooled_ws_bytes(n, n_sets));
+        return RD_ERR_WS;
+    }
+    SetSpecs sp;
+    fill_specs(sp, n_sets, nullptr, set_need, set_thr);
+    hipStream_t s = (hipStream_t)s_;
+    const int nbm = sets_moment_blocks(n), nbh = sets_hist_blocks(n);
+    StatsWs w;
+    stats_ws_layout(n, ws, &w);
+    const SelectPlan plan = make_select_plan(n_sets);
+    const double pass_bytes = (double)n * (8.0 * (p1 - p0) + 1.0 + (valid ? 2.0 : 0.0));
+    {
+        ProfScope ps(s, "residual_stats_pooled|moments", 0, pass_bytes);
+        RD_LAUNCH(sets_zero_kernel, dim3(1), dim3(256), 0, s, w.hist, SEL_GROUP * 512);
+        RD_LAUNCH(pooled_moments_kernel, dim3(nbm), dim3(256), 0, s, src, (long)plane_stride, p0, p1, cls, valid, (long)n, sp,
+                  w.partial);
+        RD_LAUNCH(sets_moments_finish_kernel, dim3(n_sets), dim3(256), 0, s, (const double*)w.partial, nbm, n_sets, out, w.st);
+    }
+    // one profiler class per width of the pool, so a single-plane pass and a pooled pass are timed apart
+    char cls_name[48];
+    snprintf(cls_name, sizeof cls_name, "residual_stats_pooled|select x%d", p1 - p0);
+    ProfScope ps(s, cls_name, 0, pass_bytes * 8 * plan.ng);
+    run_selection(s, plan, n_sets, out, w.st, w.hist, [&](const SelGroup& g, int pass) {
+        RD_LAUNCH(pooled_hist_kernel, dim3(nbh), dim3(512), 0, s, src, (long)plane_stride, p0, p1, cls, valid, (long)n, sp, g,
+                  pass, (const SelState*)w.st, w.hist);
+    });
+    RD_LAUNCH_CHECK("residual_stats_pooled");
     return RD_OK;
 }
 
@@ -821,296 +1096,6 @@ int rd_fuse_planes(const double* planes, long long plane_stride, int n_planes, l
 #undef RD_FUSE_CASE
     }
     RD_LAUNCH_CHECK("fuse_planes");
-    return RD_OK;
-}
-
-}  // extern "C"
-
-// ---- evaluation of the P planes of a pair sweep where the sweep left them (include/resdepth_hip_eval.h) -------------------
-// rd_eval_classify_planes: eval_classify_kernel with the prediction replaced by P planes (and an optional extra surface, the
-// fused one): everything that does not depend on the plane -- area rectangles, ground-truth validity, the class bits -- is
-// worked out once per pixel; per plane one load, one subtraction, one store and one bit of the validity word.  The planes are
-// walked with a running pointer, one value live at a time: no array of P values, so nothing is indexed by a runtime number
-// (scripts/check_isa.sh fails the build on scratch).  The residual planes may be the input planes: a thread reads plane p of
-// its pixel before it writes it and no other thread touches that element, so neither pointer is __restrict__.
-//
-// rd_residual_stats_pooled: rd_residual_stats_sets with a set's members drawn from planes p0 .. p1 - 1 of one strided source.
-// The per-pixel class byte and validity word are read once per round and serve every plane and every selector; the plane
-// loop is the outer one, so a round holds HB values of ONE plane in registers (indexed by the unrolled u only).  Moments,
-// selection states, the pick / finish kernels and the workspace layout are those of rd_residual_stats_sets.
-namespace rd {
-
-__global__ __launch_bounds__(256) void eval_classify_planes_kernel(
-    const double* planes, long plane_stride, int n_planes, const double* extra, const void* __restrict__ init, int init_f64,
-    const void* __restrict__ gt, int gt_f64, const uint8_t* __restrict__ gt_mask, const uint8_t* __restrict__ bdil,
-    const uint8_t* __restrict__ bnod, const uint8_t* __restrict__ water, const uint8_t* __restrict__ forest, EvalRects area,
-    int rows, int cols, double nodata, double* __restrict__ rb, double* res, double* r_extra, uint8_t* __restrict__ cls,
-    uint16_t* __restrict__ valid) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= cols) return;
-    for (int y = blockIdx.y; y < rows; y += gridDim.y) {
-        const long i = (long)y * cols + x;
-        bool in = area.n < 0;
-        for (int q = 0; q < area.n; ++q)
-            in |= y >= area.r[q][0] && y < area.r[q][1] && x >= area.r[q][2] && x < area.r[q][3];
-        const double g = load_f(gt, gt_f64, i), a = load_f(init, init_f64, i);
-        const bool gok = in && g != nodata && (!gt_mask || gt_mask[i]);
-        unsigned c = 0;
-        if (gok && a != nodata) c |= RD_CLS_VALID_BEFORE;
-        if (bdil) {
-            const bool b = bdil[i] != 0;
-            const bool t = in && !b && !(bnod && bnod[i]);
-            const bool tw = t && !(water && water[i]);
-            if (in && b) c |= RD_CLS_BUILDING;
-            if (t) c |= RD_CLS_TERRAIN;
-            if (tw) c |= RD_CLS_TERRAIN_NOWATER;
-            if (tw && !(forest && forest[i])) c |= RD_CLS_TERRAIN_NOWATER_NOFOREST;
-        }
-        if (extra) {
-            const double e = extra[i];
-            if (gok && e != nodata) c |= RD_CLS_VALID_EXTRA;
-            r_extra[i] = e - g;
-        }
-        unsigned v = 0;
-        const double* src = planes + i;
-        double* dst = res + i;
-        for (int p = 0; p < n_planes; ++p, src += plane_stride, dst += plane_stride) {
-            const double pv = *src;
-            if (gok && pv != nodata) v |= 1u << p;
-            *dst = pv - g;
-        }
-        if (rb) rb[i] = a - g;
-        cls[i] = (uint8_t)c;
-        valid[i] = (uint16_t)v;
-    }
-}
-
-// sets_moments_kernel over planes p0 .. p1 - 1: a thread adds its pixels in pixel order and, per pixel, in plane order
-__global__ __launch_bounds__(256) void pooled_moments_kernel(const double* __restrict__ src, long plane_stride, int p0, int p1,
-                                                             const uint8_t* __restrict__ cls,
-                                                             const uint16_t* __restrict__ valid, long n, SetSpecs sp,
-                                                             double* __restrict__ partial) {
-    double cnt[RD_STATS_MAX_SETS], sa[RD_STATS_MAX_SETS], sq[RD_STATS_MAX_SETS], mn[RD_STATS_MAX_SETS],
-        mx[RD_STATS_MAX_SETS];
-#pragma unroll
-    for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
-        cnt[s] = sa[s] = sq[s] = 0.0;
-        mn[s] = INFINITY;
-        mx[s] = -INFINITY;
-    }
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const unsigned c = cls[i];
-        const unsigned v = valid ? (unsigned)valid[i] : 0xffffu;
-        const double* q = src + (long)p0 * plane_stride + i;
-        for (int p = p0; p < p1; ++p, q += plane_stride) {
-            if (!((v >> p) & 1u)) continue;
-            const double d = *q;
-#pragma unroll
-            for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
-                if (s < sp.n && in_set(sp, s, c, d)) {
-                    cnt[s] += 1.0;
-                    sa[s] += fabs(d);
-                    sq[s] += d * d;
-                    mn[s] = fmin(mn[s], d);
-                    mx[s] = fmax(mx[s], d);
-                }
-            }
-        }
-    }
-    __shared__ double red[4][5];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int s = 0; s < RD_STATS_MAX_SETS; ++s) {
-        if (s >= sp.n) continue;
-        const double v0 = wave_sum(cnt[s]), v1 = wave_sum(sa[s]), v2 = wave_sum(sq[s]), v3 = wave_min(mn[s]),
-                     v4 = wave_max(mx[s]);
-        if (lane == 0) {
-            red[w][0] = v0; red[w][1] = v1; red[w][2] = v2; red[w][3] = v3; red[w][4] = v4;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double* o = partial + ((long)blockIdx.x * sp.n + s) * 5;
-            o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-            o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-            o[2] = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-            o[3] = fmin(fmin(red[0][3], red[1][3]), fmin(red[2][3], red[3][3]));
-            o[4] = fmax(fmax(red[0][4], red[1][4]), fmax(red[2][4], red[3][4]));
-        }
-        __syncthreads();
-    }
-}
-
-// sets_hist_kernel over planes p0 .. p1 - 1 (the histogram layout is that kernel's): per round the class bytes and validity
-// words of HB pixels are read once; per plane the HB values, and the class with the plane's validity folded in (-1 = skip)
-__global__ __launch_bounds__(512) void pooled_hist_kernel(const double* __restrict__ src, long plane_stride, int p0, int p1,
-                                                          const uint8_t* __restrict__ cls, const uint16_t* __restrict__ valid,
-                                                          long n, SetSpecs sp, SelGroup g, int pass,
-                                                          const SelState* __restrict__ st, unsigned* __restrict__ hist) {
-    __shared__ unsigned lh[SEL_GROUP * 512];
-    __shared__ unsigned long long pf[SEL_GROUP][2];
-    __shared__ double sh[SEL_GROUP];
-    for (int i = threadIdx.x; i < g.n * 512; i += blockDim.x) lh[i] = 0u;
-    if (threadIdx.x < g.n) {
-        const SelState& t = st[g.set[threadIdx.x] * 3 + g.mode[threadIdx.x]];
-        pf[threadIdx.x][0] = t.prefix[0];
-        pf[threadIdx.x][1] = t.prefix[1];
-        sh[threadIdx.x] = t.shift;
-    }
-    __syncthreads();
-    const int hs = 8 * (pass + 1);
-    const long step = (long)gridDim.x * blockDim.x * HB;
-    for (long base = (long)blockIdx.x * blockDim.x * HB + threadIdx.x; base < n; base += step) {
-        int c0[HB];
-        unsigned v[HB];
-#pragma unroll
-        for (int u = 0; u < HB; ++u) {
-            const long i = base + (long)u * blockDim.x;
-            const bool ok = i < n;
-            c0[u] = ok ? (int)cls[i] : -1;
-            v[u] = ok ? (valid ? (unsigned)valid[i] : 0xffffu) : 0u;
-        }
-        const double* q = src + (long)p0 * plane_stride;
-        for (int p = p0; p < p1; ++p, q += plane_stride) {
-            double r[HB];
-            int c[HB];
-#pragma unroll
-            for (int u = 0; u < HB; ++u) {
-                const long i = base + (long)u * blockDim.x;
-                const bool ok = c0[u] >= 0 && ((v[u] >> p) & 1u);
-                r[u] = ok ? q[i] : 0.0;
-                c[u] = ok ? c0[u] : -1;
-            }
-            for (int j = 0; j < g.n; ++j) {
-                const int s = g.set[j], mode = g.mode[j];
-                const int need = (int)sp.need[s];
-                const double thr = sp.thr[s], shift = sh[j];
-                const unsigned long long pa = pf[j][0], pb = pf[j][1];
-                unsigned* h = lh + j * 512;
-#pragma unroll
-                for (int u = 0; u < HB; ++u) {
-                    if (c[u] < 0 || (c[u] & need) != need || (thr > 0.0 && !(fabs(r[u]) <= thr))) continue;
-                    const unsigned long long k = key_of(pick_value(r[u], mode, shift));
-                    const unsigned long long hi = pass == 7 ? 0ull : (k >> hs);
-                    const unsigned b = (unsigned)((k >> (8 * pass)) & 255ull);
-                    if (hi == pa)
-                        atomicAdd(&h[b], 1u);
-                    else if (hi == pb)
-                        atomicAdd(&h[256 + b], 1u);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < g.n * 512; i += blockDim.x)
-        if (lh[i]) atomicAdd(&hist[i], lh[i]);
-}
-
-}  // namespace rd
-
-extern "C" {
-
-int rd_eval_classify_planes(const double* planes, long long plane_stride, int n_planes, const double* extra,
-                            const void* initial, int initial_f64, const void* gt, int gt_f64, const uint8_t* gt_mask,
-                            const uint8_t* building, const uint8_t* building_nodata, const uint8_t* water,
-                            const uint8_t* forest, const int* rects, int n_rects, int rows, int cols, double nodata,
-                            double* r_before, double* residuals, double* r_extra, uint8_t* cls, uint16_t* valid,
-                            rd_stream_t s_) {
-    RD_REQUIRE(planes && initial && gt && residuals && cls && valid && rows > 0 && cols > 0,
-               "rd_eval_classify_planes: bad arguments");
-    RD_REQUIRE(n_planes >= 1 && n_planes <= RD_EVAL_MAX_PLANES, "rd_eval_classify_planes: n_planes must be in 1..%d (got %d)",
-               RD_EVAL_MAX_PLANES, n_planes);
-    RD_REQUIRE(plane_stride >= (long long)rows * cols, "rd_eval_classify_planes: plane_stride %lld < rows * cols = %lld",
-               plane_stride, (long long)rows * cols);
-    RD_REQUIRE(!extra == !r_extra, "rd_eval_classify_planes: extra and r_extra come together");
-    RD_REQUIRE(n_rects <= RD_EVAL_MAX_RECTS && (n_rects <= 0 || rects),
-               "rd_eval_classify_planes: %d area rectangles (at most %d)", n_rects, RD_EVAL_MAX_RECTS);
-    EvalRects area;
-    area.n = n_rects;
-    for (int q = 0; q < n_rects; ++q)
-        for (int e = 0; e < 4; ++e) area.r[q][e] = rects[q * 4 + e];
-    hipStream_t s = (hipStream_t)s_;
-    const double n = (double)rows * cols;
-    ProfScope ps(s, "eval_classify_planes", 0,
-                 n * (16.0 * (n_planes + (extra ? 1 : 0)) + (initial_f64 ? 8 : 4) + (gt_f64 ? 8 : 4) + (r_before ? 8.0 : 0.0) + 3.0));
-    const dim3 grid((cols + 255) / 256, rows < 65535 ? rows : 65535);
-    RD_LAUNCH(eval_classify_planes_kernel, grid, dim3(256), 0, s, planes, (long)plane_stride, n_planes, extra, initial,
-              initial_f64 ? 1 : 0, gt, gt_f64 ? 1 : 0, gt_mask, building, building_nodata, water, forest, area, rows, cols,
-              nodata, r_before, residuals, r_extra, cls, valid);
-    RD_LAUNCH_CHECK("eval_classify_planes");
-    return RD_OK;
-}
-
-size_t rd_residual_stats_pooled_ws_bytes(long long n, int n_sets) { return rd_residual_stats_sets_ws_bytes(n, n_sets); }
-
-int rd_residual_stats_pooled(const double* src, long long plane_stride, int n_planes, int p0, int p1, const uint8_t* cls,
-                             const uint16_t* valid, long long n, const int* set_need, const double* set_thr, int n_sets,
-                             double* out, void* ws, size_t ws_bytes, rd_stream_t s_) {
-    RD_REQUIRE(src && cls && out && n > 0 && set_need && set_thr, "rd_residual_stats_pooled: bad arguments");
-    RD_REQUIRE(n_planes >= 1 && n_planes <= RD_EVAL_MAX_PLANES, "rd_residual_stats_pooled: n_planes must be in 1..%d (got %d)",
-               RD_EVAL_MAX_PLANES, n_planes);
-    RD_REQUIRE(p0 >= 0 && p0 < p1 && p1 <= n_planes, "rd_residual_stats_pooled: planes [%d, %d) outside the %d planes", p0, p1,
-               n_planes);
-    RD_REQUIRE(plane_stride >= n, "rd_residual_stats_pooled: plane_stride %lld < n = %lld", plane_stride, n);
-    RD_REQUIRE(n_sets >= 1 && n_sets <= RD_STATS_MAX_SETS, "rd_residual_stats_pooled: %d sets (1..%d)", n_sets,
-               RD_STATS_MAX_SETS);
-    // the histograms are 32-bit counters: a bin may hold every member of a set
-    RD_REQUIRE(n < (1ll << 32) && (long long)(p1 - p0) * n < (1ll << 32),
-               "rd_residual_stats_pooled: (p1 - p0) * n = %d * %lld values reach 2^32 (32-bit histogram counters)", p1 - p0, n);
-    if (!ws || ws_bytes < rd_residual_stats_pooled_ws_bytes(n, n_sets)) {
-        set_error("rd_residual_stats_pooled: workspace too small (%zu < %zu)", ws_bytes,
-                  rd_residual_stats_pooled_ws_bytes(n, n_sets));
-        return RD_ERR_WS;
-    }
-    SetSpecs sp;
-    sp.n = n_sets;
-    for (int i = 0; i < RD_STATS_MAX_SETS; ++i) {
-        sp.src[i] = 0;
-        sp.need[i] = i < n_sets ? (unsigned)set_need[i] : 0u;
-        sp.thr[i] = i < n_sets ? set_thr[i] : -1.0;
-    }
-    hipStream_t s = (hipStream_t)s_;
-    const int nbm = sets_moment_blocks(n), nbh = sets_hist_blocks(n);
-    char* base = (char*)ws;
-    double* partial = (double*)base;
-    SelState* st = (SelState*)(base + (size_t)nbm * RD_STATS_MAX_SETS * 5 * sizeof(double));
-    unsigned* hist = (unsigned*)((char*)st + (size_t)RD_STATS_MAX_SETS * 3 * sizeof(SelState));
-    SelGroup groups[3 * RD_STATS_MAX_SETS / SEL_GROUP + 3];
-    int phase_end[2] = {0, 0}, ng = 0;
-    for (int phase = 0; phase < 2; ++phase) {
-        const int nsel = phase == 0 ? 2 * n_sets : n_sets;
-        for (int j0 = 0; j0 < nsel; j0 += SEL_GROUP) {
-            SelGroup& g = groups[ng++];
-            g.n = nsel - j0 < SEL_GROUP ? nsel - j0 : SEL_GROUP;
-            for (int j = 0; j < SEL_GROUP; ++j) {
-                const int q = j0 + (j < g.n ? j : 0);
-                g.set[j] = phase == 0 ? q >> 1 : q;
-                g.mode[j] = phase == 0 ? (q & 1) : 2;
-            }
-        }
-        phase_end[phase] = ng;
-    }
-    const double pass_bytes = (double)n * (8.0 * (p1 - p0) + 1.0 + (valid ? 2.0 : 0.0));
-    {
-        ProfScope ps(s, "residual_stats_pooled|moments", 0, pass_bytes);
-        RD_LAUNCH(sets_zero_kernel, dim3(1), dim3(256), 0, s, hist, SEL_GROUP * 512);
-        RD_LAUNCH(pooled_moments_kernel, dim3(nbm), dim3(256), 0, s, src, (long)plane_stride, p0, p1, cls, valid, (long)n, sp,
-                  partial);
-        RD_LAUNCH(sets_moments_finish_kernel, dim3(n_sets), dim3(256), 0, s, (const double*)partial, nbm, n_sets, out, st);
-    }
-    // one profiler class per width of the pool, so a single-plane pass and a pooled pass are timed apart
-    char cls_name[48];
-    snprintf(cls_name, sizeof cls_name, "residual_stats_pooled|select x%d", p1 - p0);
-    ProfScope ps(s, cls_name, 0, pass_bytes * 8 * ng);
-    for (int gi = 0; gi < ng; ++gi) {
-        if (gi == phase_end[0]) RD_LAUNCH(sets_shift_kernel, dim3(1), dim3(64), 0, s, (const double*)out, n_sets, st);
-        for (int pass = 7; pass >= 0; --pass) {
-            RD_LAUNCH(pooled_hist_kernel, dim3(nbh), dim3(512), 0, s, src, (long)plane_stride, p0, p1, cls, valid, (long)n, sp,
-                      groups[gi], pass, (const SelState*)st, hist);
-            RD_LAUNCH(sets_pick_kernel, dim3(groups[gi].n), dim3(256), 0, s, groups[gi], st, hist);
-        }
-        RD_LAUNCH(sets_select_finish_kernel, dim3(1), dim3(64), 0, s, groups[gi], (const SelState*)st, out);
-    }
-    RD_LAUNCH_CHECK("residual_stats_pooled");
     return RD_OK;
 }
 

@@ -28,14 +28,9 @@ def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=N
     """raster: refined DSM (any float dtype, e.g. the float64 output of predict_linear_blend), raster_gt: reference DSM,
     mask_gt: optional boolean validity mask.  -> dict as lib/evaluation.py:get_statistics (incl. 'truncated' sub-dict
     when residual_threshold is given)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("resdepth_amd.evaluation.get_statistics needs a HIP device (no CPU fallback)")
-    r = torch.as_tensor(np.asarray(raster) if not torch.is_tensor(raster) else raster).to(dev, torch.float64).contiguous()
-    g = torch.as_tensor(np.asarray(raster_gt) if not torch.is_tensor(raster_gt) else raster_gt).to(dev, torch.float32).contiguous()
-    m = None
-    if mask_gt is not None:
-        m = torch.as_tensor(np.asarray(mask_gt) if not torch.is_tensor(mask_gt) else mask_gt).to(dev).to(torch.uint8).contiguous()
+    dev = _device(device, "resdepth_amd.evaluation.get_statistics")
+    r, g = _on(raster, dev, torch.float64), _on(raster_gt, dev, torch.float32)
+    m = None if mask_gt is None else _on(mask_gt, dev).to(torch.uint8).contiguous()
     with torch.cuda.device(r.device):              # raw launches go to the current device's stream
         full = _stats(r, g, m, nodata, None, r.device)
         trunc = _stats(r, g, m, nodata, residual_threshold, r.device) if residual_threshold else None
@@ -68,11 +63,16 @@ class AttrDict(dict):
     __setattr__ = dict.__setitem__
 
 
-def _device(dev):
+def _device(dev, who="resdepth_amd.evaluation"):
     dev = torch.device(dev)
     if dev.type != "cuda":
-        raise RuntimeError("resdepth_amd.evaluation needs a HIP device (no CPU fallback)")
+        raise RuntimeError(f"{who} needs a HIP device (no CPU fallback)")
     return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _first_device(*xs, default):
+    """The device of the first CUDA tensor among xs, else `default`."""
+    return _device(next((x.device for x in xs if torch.is_tensor(x) and x.is_cuda), default))
 
 
 def _on(x, dev, dtype=None):
@@ -142,14 +142,19 @@ def _rects(area_defn, rows, cols):
     return out
 
 
+def _set_arrays(sets):
+    """[([source,] need bits, threshold or None)] -> the ctypes arrays (need, thr[, src]) of a statistics call."""
+    ns = len(sets)
+    need_a = (ctypes.c_int * ns)(*[s[-2] for s in sets])
+    thr_a = (ctypes.c_double * ns)(*[float(s[-1]) if s[-1] else -1.0 for s in sets])
+    return (need_a, thr_a) if len(sets[0]) == 2 else (need_a, thr_a, (ctypes.c_int * ns)(*[s[0] for s in sets]))
+
+
 def _run_sets(src0, src1, cls, sets, dev):
     """sets: [(source, need bits, threshold or None)] -> host float64 array [len(sets), 8] (rd_residual_stats_sets)."""
-    n = cls.numel()
-    ns = len(sets)
+    n, ns = cls.numel(), len(sets)
     lib = load()
-    src_a = (ctypes.c_int * ns)(*[s for s, _, _ in sets])
-    need_a = (ctypes.c_int * ns)(*[b for _, b, _ in sets])
-    thr_a = (ctypes.c_double * ns)(*[float(t) if t else -1.0 for _, _, t in sets])
+    need_a, thr_a, src_a = _set_arrays(sets)
     out = torch.empty((ns, 8), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         ws = workspace(lib.rd_residual_stats_sets_ws_bytes(n, ns), dev, slot=3)
@@ -166,6 +171,12 @@ def _stats_dict(full, trunc, thr):
                                 absolute_median=float(trunc[5]), median=float(trunc[6]), NMAD=float(trunc[7]))
     st.update(zip(_KEYS, (float(v) for v in full)))
     return st
+
+
+def _class_stats(rows, classes, thr):
+    """rows [len(classes) * (2 if thr else 1), 8] in class order (full, truncated) -> {class: stats}."""
+    step = 2 if thr else 1
+    return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr)) for q, c in enumerate(classes))
 
 
 def _float_raster(x, dev):
@@ -219,20 +230,12 @@ def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_w
                                    int(g.dtype == torch.float64), ptr(gm), ptr(bdil), ptr(bnod), ptr(water), ptr(forest),
                                    rect_a, n_rects, rows, cols, nd, ptr(r_before), ptr(r_after), ptr(cls), stream_ptr()),
               "eval_classify")
-    sets = []
-    for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)):
-        for c in classes:
-            sets.append((src, valid | CLASS_BITS[c], None))
-            if residual_threshold:
-                sets.append((src, valid | CLASS_BITS[c], residual_threshold))
+    thr = residual_threshold
+    sets = [(src, valid | CLASS_BITS[c], t) for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)) for c in classes
+            for t in ((None, thr) if thr else (None,))]
     res = _run_sets(r_before, r_after, cls, sets, dev)
-    stats = AttrDict(before=AttrDict(), after=AttrDict())
-    step = 2 if residual_threshold else 1
-    for q, (src, need, _) in enumerate(sets[::step]):
-        c = classes[q % len(classes)]
-        row = q * step
-        stats["after" if src else "before"][c] = _stats_dict(res[row], res[row + 1] if step == 2 else None,
-                                                             residual_threshold)
+    half = len(sets) // 2                              # source-major: the initial DSM's rows, then the refined DSM's
+    stats = AttrDict(before=_class_stats(res[:half], classes, thr), after=_class_stats(res[half:], classes, thr))
     return stats, r_after, cls, classes
 
 
@@ -246,12 +249,7 @@ def evaluate_statistics(prediction, initial, gt, area_defn=None, mask_gt=None, m
     read as given).  nodata: the ground truth's nodata value (None: none).  Masks: arrays / tensors (value 1 = set),
     (values, nodata) tuples or dataset-like objects; water and forest only count with a building mask.
     -> {'before': {class: stats}, 'after': {class: stats}} in the reference's get_statistics format, attribute access."""
-    dev = None
-    for x in (prediction, initial, gt):
-        if torch.is_tensor(x) and x.is_cuda:
-            dev = x.device
-            break
-    dev = _device(dev if dev is not None else device)
+    dev = _first_device(prediction, initial, gt, default=device)
     return _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest,
                      residual_threshold, nodata, dev)[0]
 
@@ -449,17 +447,10 @@ def _queue_pooled(res, n_planes, p0, p1, cls, valid, sets, out, dev):
     only.  sets: [(need bits, threshold or None)]."""
     n, ns = cls.numel(), len(sets)
     lib = load()
-    need_a = (ctypes.c_int * ns)(*[b for b, _ in sets])
-    thr_a = (ctypes.c_double * ns)(*[float(t) if t else -1.0 for _, t in sets])
+    need_a, thr_a = _set_arrays(sets)
     ws = workspace(lib.rd_residual_stats_pooled_ws_bytes(n, ns), dev, slot=3)
     check(lib.rd_residual_stats_pooled(ptr(res), n, n_planes, p0, p1, ptr(cls), ptr(valid), n, need_a, thr_a, ns, ptr(out),
                                        ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats_pooled")
-
-
-def _class_stats(rows, classes, thr):
-    """rows [len(classes) * (2 if thr else 1), 8] in class order (full, truncated) -> {class: stats}."""
-    step = 2 if thr else 1
-    return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr)) for q, c in enumerate(classes))
 
 
 def _is_sweep(x):
@@ -485,12 +476,7 @@ def _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_
         if fused is None:
             fused = getattr(sweep, "device_fused", None)
             fused = sweep.fused if fused is None else fused
-    dev = None
-    for x in (pairs, fused, initial, gt):
-        if torch.is_tensor(x) and x.is_cuda:
-            dev = x.device
-            break
-    dev = _device(dev if dev is not None else device)
+    dev = _first_device(pairs, fused, initial, gt, default=device)
     if len(pairs.shape) != 3:
         raise ValueError(f"evaluate_pairs: pairs must be [P, rows, cols] (got shape {tuple(pairs.shape)})")
     n_planes = int(pairs.shape[0])

@@ -646,4 +646,5 @@ int rd_prof_collect(rd_prof_entry* out, int max_entries); /* returns number of c
 #include "resdepth_hip_tta.h" /* test-time augmentation: oriented grid tiles and the blend that undoes the orientation */
 #include "resdepth_hip_pairs.h" /* all image pairs in one sweep: the blend into planes and the per-pixel fusion */
 #include "resdepth_hip_eval.h" /* scoring the planes of a pair sweep: classification of P planes, statistics pooled over planes */
+#include "resdepth_hip_loss.h" /* masked L2 / Huber / slope-consistency training losses and the MAE beside them */
 #endif /* RESDEPTH_HIP_H */

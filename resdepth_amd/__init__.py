@@ -4,7 +4,7 @@ Python host surface mirroring the reference (UNet / Trainer / batch dict), hand-
 underneath (libresdepth_hip.so, C ABI in include/resdepth_hip.h).  No CPU fallback.
 """
 from .unet import UNet, SkipConnection  # noqa: F401
-from .loss import MaskedL1Loss, masked_l1_loss  # noqa: F401
+from .loss import MaskedL1Loss, MaskedLoss, masked_l1_loss, masked_loss  # noqa: F401
 from .optim import FusedAdam, FusedSGD, get_optimizer  # noqa: F401
 from .trainer import Trainer, AverageMeter, DevicePrefetcher  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
@@ -19,7 +19,7 @@ from .evaluation import (dilate_mask, evaluate_pairs_performance, evaluate_pairs
 from .factories import (get_loss, get_model, get_scheduler, get_trainer, valid_tile_size,  # noqa: F401
                         validate_tile_size)
 
-__all__ = ["UNet", "SkipConnection", "MaskedL1Loss", "masked_l1_loss", "FusedAdam", "FusedSGD", "get_optimizer", "Trainer", "AverageMeter", "DevicePrefetcher", "GraphedTrainStep", "PlannedTrainStep",
+__all__ = ["UNet", "SkipConnection", "MaskedL1Loss", "masked_l1_loss", "MaskedLoss", "masked_loss", "FusedAdam", "FusedSGD", "get_optimizer", "Trainer", "AverageMeter", "DevicePrefetcher", "GraphedTrainStep", "PlannedTrainStep",
            "SyntheticDsmOrthoDataset", "synthetic_batch", "predict_linear_blend", "SyntheticRasterTiles", "predict_pairs_linear_blend", "PairSweep",
            "GpuPatchSampler", "SamplerLoader", "GpuGridTiles", "GpuTrainSet", "GpuValSet", "normalization", "get_loss", "get_model", "get_scheduler", "get_trainer", "valid_tile_size", "validate_tile_size",
            "dilate_mask", "evaluate_statistics", "evaluate_performance", "print_statistics", "get_statistics_masked",

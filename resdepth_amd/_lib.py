@@ -174,6 +174,15 @@ SIGNATURES_EVAL = {
     "rd_residual_stats_pooled_ws_bytes": (SZ, [LL, I]),
     "rd_residual_stats_pooled": (I, [P, LL, I, I, I, P, P, LL, P, P, I, P, P, SZ, P]),
 }
+# include/resdepth_hip_loss.h (masked L2 / Huber / slope-consistency losses), one to one as above
+SIGNATURES_LOSS = {
+    "rd_masked_loss_ws_bytes": (SZ, [I, I, I]),
+    "rd_masked_loss_partial": (I, [P, P, P, P, P, P, I, I, I, I, D, D, P, SZ, P]),
+    "rd_masked_loss_finish": (I, [P, P, P, P, P, P, D, I, D, D, D, P, P, P, P, I, I, I, P]),
+}
+# the constants of that header
+LOSS_KINDS = {"l1": 0, "l2": 1, "huber": 2}
+LOSS_STRIP_ROWS, LOSS_STRIP_COLS, LOSS_MAX_BLOCKS = 32, 64, 1024
 
 
 class ProfEntry(C.Structure):
@@ -195,7 +204,7 @@ def load():
                 "there is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
-                + list(SIGNATURES_EVAL.items()):
+                + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -24,13 +24,17 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .loss import masked_l1_loss
+from .loss import masked_l1_loss, masked_loss
 from .optim import FusedAdam
 
 
 class GraphedTrainStep:
-    def __init__(self, model, optimizer, warmup: int = 2, keep_grads: bool = False):
+    def __init__(self, model, optimizer, warmup: int = 2, keep_grads: bool = False, loss=None):
         self.model, self.optimizer = model, optimizer
+        # loss: None = masked_l1_loss; a resdepth_amd.MaskedLoss = that loss, with the batch's masked MAE kept in `mae` the way
+        # the loss is kept (after a replay: the graph's own buffer)
+        self.loss = loss
+        self.mae = None
         self.warmup = max(1, int(warmup))        # >= 1: the moments and the flat gradient buffer exist after one eager step
         self.keep_grads = keep_grads             # leave p.grad pointing at the graph's gradient buffers (default: None, as the reference)
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
@@ -39,6 +43,7 @@ class GraphedTrainStep:
         self._key = None
         self._static = None
         self._loss = None
+        self._mae = None                         # the captured iteration's MAE buffer (loss is a MaskedLoss)
         self._grads = None
         self._cap_token = None
         self._stream = None                      # the capture stream, with a split-K scratch of its own (_lib.pin_splitk_workspace)
@@ -56,13 +61,23 @@ class GraphedTrainStep:
         for p in self.params:
             p.grad = None
         out = self.model(x)
-        loss = masked_l1_loss(out, y, mask, mean, std, grad_sync=getattr(self.model, "grad_sync", None))
+        loss = self._criterion(out, y, mask, mean, std)
         loss.backward()
         self.optimizer.step()
         if not self.keep_grads:
             for p in self.params:
                 p.grad = None
         return loss.detach()
+
+    def _criterion(self, out, y, mask, mean, std):
+        """The iteration's loss; leaves the masked MAE of a MaskedLoss in `mae`."""
+        gs = getattr(self.model, "grad_sync", None)
+        if self.loss is None:
+            return masked_l1_loss(out, y, mask, mean, std, grad_sync=gs)
+        m = self.loss
+        loss, self.mae = masked_loss(out, y, mask, mean, std, m.kind, m.delta, m.slope_weight,
+                                     grad_sync=m.grad_sync if m.grad_sync is not None else gs, return_mae=True)
+        return loss
 
     # ---- hooks of the launch-plan variant (resdepth_amd/plan.py) -----------------------------------------------------------
     def _record_begin(self):
@@ -98,7 +113,7 @@ class GraphedTrainStep:
 
     def invalidate(self):
         """Drop the captured graph (the next eligible call captures again)."""
-        self._graph = self._static = self._loss = self._grads = self._key = self._cap_token = self._ws_held = None
+        self._graph = self._static = self._loss = self._mae = self._grads = self._key = self._cap_token = self._ws_held = None
 
     def __del__(self):
         try:
@@ -130,13 +145,14 @@ class GraphedTrainStep:
             self._record_begin()
             try:
                 out = self.model(static[0])
-                loss = masked_l1_loss(out, static[1], static[2], static[3], static[4], grad_sync=getattr(self.model, "grad_sync", None))
+                loss = self._criterion(out, static[1], static[2], static[3], static[4])
                 loss.backward(self._one)
                 self.optimizer.capture_step()
                 sloss = loss.detach()
             finally:
                 self._record_end()
         self._graph, self._static, self._loss = g, static, sloss
+        self._mae = self.mae if self.loss is not None else None
         self._grads = [p.grad for p in self.params]
         self._key = self._shape_key(batch)
         self._cap_token = self.optimizer._cap
@@ -202,4 +218,5 @@ class GraphedTrainStep:
             else:
                 for p in self.params:
                     p.grad = None
+        self.mae = self._mae
         return self._loss

@@ -7,8 +7,14 @@ lib/data_normalization.py:29-38).
 
 Data-parallel: the normaliser sum(mask) and numel are GLOBAL (all ranks), so the two partial sums are
 all-reduced between the reduction and the finishing kernel.
+
+`masked_loss` / `MaskedLoss` are the same chain for the other criteria the reference's generic expression takes -- nn.MSELoss,
+nn.HuberLoss, nn.SmoothL1Loss -- plus an optional slope-consistency term on the residual's first differences, with the masked
+MAE reported beside the loss (include/resdepth_hip_loss.h).
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -80,3 +86,112 @@ class MaskedL1Loss(torch.nn.Module):
 
     def forward(self, y_pred, y, loss_mask, mean, std):
         return masked_l1_loss(y_pred, y, loss_mask, mean, std, self.grad_sync)
+
+
+# ---- L2 / Huber / smooth-L1 data terms and the slope-consistency term -------------------------------------------------------
+KINDS = ("l1", "l2", "huber", "smooth_l1")
+
+
+def _check_spec(kind, delta, slope_weight):
+    """Host-side validation (no device use); returns the canonical (kind, delta, slope_weight)."""
+    if kind not in KINDS:
+        raise ValueError(f"kind={kind!r}: expected one of {', '.join(KINDS)}")
+    delta, slope_weight = float(delta), float(slope_weight)
+    if kind == "smooth_l1" and delta == 0.0:
+        kind, delta = "l1", 1.0                  # nn.SmoothL1Loss(beta=0) is L1
+    if kind in ("huber", "smooth_l1") and not (delta > 0.0 and math.isfinite(delta)):
+        raise ValueError(f"delta={delta!r}: the {kind} threshold must be positive and finite")
+    if not (slope_weight >= 0.0 and math.isfinite(slope_weight)):
+        raise ValueError(f"slope_weight={slope_weight!r}: must be finite and >= 0")
+    return kind, delta, slope_weight
+
+
+def _kernel_args(kind, delta):
+    """(kind code, delta, scale) of the C ABI: smooth_l1(beta) is huber(beta) / beta."""
+    if kind == "smooth_l1":
+        return _lib.LOSS_KINDS["huber"], delta, 1.0 / delta
+    return _lib.LOSS_KINDS[kind], delta, 1.0
+
+
+class _MaskedLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y_pred, y, mask_u8, mean, std, grad_sync, kind, delta, scale, slope_weight):
+        with _lib.device_of(y_pred):
+            sums = ops.masked_loss_partial(y_pred, y, mask_u8, mean, std, kind, delta, scale)
+            numel = y_pred.numel()
+            if grad_sync is not None:
+                numel = grad_sync.allreduce_loss_sums(sums, numel)
+            loss, mae, _ = ops.masked_loss_finish(y_pred, y, mask_u8, mean, std, sums, numel, kind, delta, scale, slope_weight,
+                                                  want_grad=False)
+        ctx.save_for_backward(y_pred, y, mask_u8, mean, std, sums)
+        ctx.spec = (numel, kind, delta, scale, slope_weight)
+        loss, mae = loss.reshape(()), mae.reshape(())
+        ctx.mark_non_differentiable(mae)
+        return loss, mae
+
+    @staticmethod
+    def backward(ctx, gout, _gmae):
+        y_pred, y, mask_u8, mean, std, sums = ctx.saved_tensors
+        numel, kind, delta, scale, slope_weight = ctx.spec
+        g = gout.detach().to(torch.float32).contiguous()      # stays on the device: the kernel reads it through a pointer
+        with _lib.device_of(y_pred):
+            _, _, dyp = ops.masked_loss_finish(y_pred, y, mask_u8, mean, std, sums, numel, kind, delta, scale, slope_weight,
+                                               gout=g, want_loss=False, want_mae=False)
+        return (dyp,) + (None,) * 9
+
+
+def masked_loss(y_pred, y, loss_mask, mean, std, kind="l1", delta=1.0, slope_weight=0.0, grad_sync=None, return_mae=False):
+    """loss = sum(m rho(r)) / sum(m) + slope_weight * sum|r_a - r_b| / #pairs over the valid horizontal and vertical neighbour
+    pairs, r the de-normalised residual; rho by `kind`: "l1", "l2", "huber" (delta, in metres), "smooth_l1" (beta = delta).
+    Returns the 0-dim device loss with autograd to y_pred; with return_mae also the masked MAE (0-dim, no gradient).
+    kind="l1" with slope_weight=0 IS masked_l1_loss (its kernels, its bits)."""
+    kind, delta, slope_weight = _check_spec(kind, delta, slope_weight)
+    if slope_weight > 0.0 and not (y_pred.dim() == 4 and y_pred.shape[1] == 1):
+        raise ValueError(f"y_pred of shape {tuple(y_pred.shape)}: slope_weight > 0 needs a 4-D [N,1,H,W] input (neighbour "
+                         "pairs are taken inside one single-channel image)")
+    if kind == "l1" and slope_weight == 0.0:
+        loss = masked_l1_loss(y_pred, y, loss_mask, mean, std, grad_sync)
+        return (loss, loss.detach()) if return_mae else loss
+    yp, y, m, mean32, std32 = _prep(y_pred, y, loss_mask, mean, std)
+    code, delta, scale = _kernel_args(kind, delta)
+    loss, mae = _MaskedLoss.apply(yp, y, m, mean32, std32, grad_sync, code, delta, scale, slope_weight)
+    return (loss, mae) if return_mae else loss
+
+
+class MaskedLoss(torch.nn.Module):
+    """Module form of masked_loss; usable as the Trainer's `criterion` and as the `loss` of GraphedTrainStep /
+    PlannedTrainStep.  After a call `last_mae` holds the masked MAE of that batch (0-dim device tensor)."""
+
+    def __init__(self, kind="l1", delta=1.0, slope_weight=0.0, grad_sync=None):
+        super().__init__()
+        _check_spec(kind, delta, slope_weight)
+        self.kind, self.delta, self.slope_weight = kind, float(delta), float(slope_weight)
+        self.grad_sync = grad_sync
+        self.last_mae = None
+
+    def extra_repr(self):
+        return f"kind={self.kind!r}, delta={self.delta}, slope_weight={self.slope_weight}"
+
+    def forward(self, y_pred, y, loss_mask, mean, std):
+        loss, self.last_mae = masked_loss(y_pred, y, loss_mask, mean, std, self.kind, self.delta, self.slope_weight,
+                                          self.grad_sync, return_mae=True)
+        return loss
+
+
+_ACCEPTED = "nn.L1Loss, nn.MSELoss, nn.HuberLoss, nn.SmoothL1Loss (each with reduction='mean') or resdepth_amd.MaskedLoss"
+
+
+def criterion_spec(criterion):
+    """(kind, delta, slope_weight) of a criterion object the fused loss can stand in for."""
+    nn = torch.nn
+    if isinstance(criterion, MaskedLoss):
+        return _check_spec(criterion.kind, criterion.delta, criterion.slope_weight)
+    table = ((nn.HuberLoss, "huber", "delta"), (nn.SmoothL1Loss, "smooth_l1", "beta"), (nn.MSELoss, "l2", None),
+             (nn.L1Loss, "l1", None))
+    for cls, kind, attr in table:
+        if type(criterion) is cls:
+            if criterion.reduction != "mean":
+                raise NotImplementedError(f"{cls.__name__}(reduction={criterion.reduction!r}): the fused loss implements "
+                                          f"reduction='mean' only; accepted: {_ACCEPTED}")
+            return _check_spec(kind, getattr(criterion, attr) if attr else 1.0, 0.0)
+    raise NotImplementedError(f"criterion {type(criterion).__name__} has no fused form; accepted: {_ACCEPTED}")

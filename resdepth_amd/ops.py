@@ -713,6 +713,41 @@ def masked_l1_finish(yp, y, mask, mean, std, sums, numel_total, gout=None, want_
     return loss, dyp
 
 
+def _loss_geometry(yp):
+    """(n, h, w) the masked-loss kernels index a batch by: [N,1,H,W] as it is; anything else as N samples of numel / N / W rows
+    of its last dimension (neighbour pairs then mean nothing: callers allow that with slope_weight == 0 only)."""
+    n = yp.shape[0]
+    w = yp.shape[-1] if yp.dim() >= 2 else 1
+    return n, yp.numel() // (n * w), w
+
+
+def masked_loss_partial(yp, y, mask, mean, std, kind=_lib.LOSS_KINDS["l2"], delta=1.0, scale=1.0):
+    """-> sums [8] float64 on device: A = sum |r|, C = #valid, D = sum rho(r), S = sum |r_a - r_b| over the valid neighbour
+    pairs, Q = their number, then zeros (include/resdepth_hip_loss.h)."""
+    n, h, w = _loss_geometry(yp)
+    sums = torch.empty(8, device=yp.device, dtype=torch.float64)
+    nb = load().rd_masked_loss_ws_bytes(n, h, w)
+    ws = workspace(nb, yp.device)
+    check(load().rd_masked_loss_partial(ptr(yp), ptr(y), ptr(mask), ptr(mean), ptr(std), ptr(sums), n, h, w, int(kind),
+                                        float(delta), float(scale), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "masked_loss_partial")
+    return sums
+
+
+def masked_loss_finish(yp, y, mask, mean, std, sums, numel_total, kind=_lib.LOSS_KINDS["l2"], delta=1.0, scale=1.0,
+                       slope_weight=0.0, gout=None, want_loss=True, want_mae=True, want_grad=True):
+    """-> (loss [1] | None, mae [1] | None, dyp | None).  gout: optional 0-dim fp32 DEVICE tensor (upstream gradient); None
+    means 1."""
+    n, h, w = _loss_geometry(yp)
+    loss = torch.empty(1, device=yp.device, dtype=torch.float32) if want_loss else None
+    mae = torch.empty(1, device=yp.device, dtype=torch.float32) if want_mae else None
+    dyp = torch.empty_like(yp) if want_grad else None
+    check(load().rd_masked_loss_finish(ptr(yp), ptr(y), ptr(mask), ptr(mean), ptr(std), ptr(sums), float(numel_total),
+                                       int(kind), float(delta), float(scale), float(slope_weight), ptr(gout), ptr(loss),
+                                       ptr(mae), ptr(dyp), n, h, w, stream_ptr()), "masked_loss_finish")
+    return loss, mae, dyp
+
+
 def adam_step(p, g, m, v, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, grad_scale=1.0):
     check(load().rd_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), beta1, beta2, eps, weight_decay, step_size,
                               bc2_sqrt, grad_scale, stream_ptr()), "adam_step")

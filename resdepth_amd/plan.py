@@ -51,8 +51,8 @@ class _Recorder:
 
 
 class PlannedTrainStep(GraphedTrainStep):
-    def __init__(self, model, optimizer, warmup: int = 2, keep_grads: bool = False, verify: bool = True):
-        super().__init__(model, optimizer, warmup, keep_grads)
+    def __init__(self, model, optimizer, warmup: int = 2, keep_grads: bool = False, verify: bool = True, loss=None):
+        super().__init__(model, optimizer, warmup, keep_grads, loss=loss)
         self._plan = None
         self._actions = None
         self._rec = None
@@ -207,21 +207,20 @@ class PlannedTrainStep(GraphedTrainStep):
         # block of Adam for THIS step was written by optimizer.advance() already; the eager reference takes the same numbers by
         # running rd_adam_step_dev through capture_step.)
         before = self._snapshot()
+        n_state = len(before)                    # got / want: the state, then the loss, then (a MaskedLoss) the MAE
         self._run_plan()
         torch.cuda.synchronize()
-        got = self._snapshot() + [self._loss.clone()]
+        got = self._snapshot() + [self._loss.clone()] + ([self._mae.clone()] if self._mae is not None else [])
         self._restore(before)
         for p in self.params:
             p.grad = None
         self.model.invalidate_packed()
         out = self.model(self._static[0])
-        from .loss import masked_l1_loss
-        loss = masked_l1_loss(out, self._static[1], self._static[2], self._static[3], self._static[4],
-                              grad_sync=getattr(self.model, "grad_sync", None))
+        loss = self._criterion(out, self._static[1], self._static[2], self._static[3], self._static[4])
         loss.backward()
         self.optimizer.capture_step()
         torch.cuda.synchronize()
-        want = self._snapshot() + [loss.detach().reshape(())]
+        want = self._snapshot() + [loss.detach().reshape(())] + ([self.mae.reshape(())] if self._mae is not None else [])
         ok = all(torch.equal(a, b) for a, b in zip(got, want))
         gs = getattr(self.model, "grad_sync", None)
         if gs is not None:                       # every rank must take the same decision
@@ -235,14 +234,16 @@ class PlannedTrainStep(GraphedTrainStep):
             if not self.keep_grads:
                 for p in self.params:
                     p.grad = None
-            taken = want[-1].clone()
+            taken = want[n_state].clone()
             self.invalidate()
             self.warmup = 1 << 62
             self.why_eager = self.plan_rejected = "the first replay did not reproduce the eager iteration bit for bit"
             return taken
         for p in self.params:
             p.grad = None
-        self._loss.copy_(want[-1])
+        self._loss.copy_(want[n_state])
+        if self._mae is not None:
+            self._mae.copy_(want[n_state + 1])
         self._verified = True
 
     def __call__(self, x, y, mask, mean, std):

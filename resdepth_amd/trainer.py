@@ -8,8 +8,11 @@ Model_best.pth / Model_last.pth / Model_after_{k}_epochs.pth (lib/Trainer.py:145
 
 What is different underneath:
   * forward/backward run on the HIP engine; the criterion + de-normalisation pair (lib/Trainer.py:87-100) is the
-    fused `masked_l1_loss` (the `criterion` argument must be an nn.L1Loss(reduction='mean'), the only loss the
-    reference offers, lib/utils.py:285);
+    fused `masked_l1_loss` for nn.L1Loss(reduction='mean') -- the only loss the reference's config offers, lib/utils.py:285 --
+    and the fused `masked_loss` for what else the reference's generic expression takes: nn.MSELoss, nn.HuberLoss,
+    nn.SmoothL1Loss (reduction='mean') and resdepth_amd.MaskedLoss (which adds the slope-consistency term).  Whatever is
+    optimised, `MAE_metric` stays the masked MAE in both phases, so best-model selection, ReduceLROnPlateau and the
+    checkpoints' loss_val compare across criteria; the train phase logs the optimised value as `loss` beside it;
   * the epoch loop keeps the per-step loss on the device and reads it back only when a value is logged
     (every `freq_average_train_loss` iterations and at epoch end) instead of one host sync per step
     (lib/Trainer.py:197); `inference_one_batch` still returns a python float as the reference does;
@@ -27,7 +30,7 @@ import time
 
 import torch
 
-from .loss import masked_l1_loss
+from .loss import MaskedLoss, criterion_spec, masked_l1_loss
 
 
 def _get(args, name, default=None):
@@ -185,15 +188,18 @@ class Trainer:
         self.optimizer = _get(args, "optimizer")
         self.scheduler = _get(args, "scheduler")
         self.criterion = _get(args, "criterion")
-        if self.criterion is not None and not (isinstance(self.criterion, torch.nn.L1Loss)
-                                                and self.criterion.reduction == "mean"):
-            raise NotImplementedError("resdepth_amd.Trainer implements the reference's L1 (mean) criterion only")
+        # what the fused loss computes for this criterion (NotImplementedError names what is accepted)
+        kind, delta, slope_weight = criterion_spec(self.criterion) if self.criterion is not None else ("l1", 1.0, 0.0)
+        plain_l1 = kind == "l1" and slope_weight == 0.0
         self.evaluate_rate = _get(args, "evaluate_rate", 1)
         self.save_model_rate = _get(args, "save_model_rate", 10 ** 9)
         self.freq_average_train_loss = _get(args, "freq_average_train_loss", 20)
         self.best_loss = math.inf
         self.index_best_loss = math.inf
         self.grad_sync = getattr(self.model, "grad_sync", None)
+        # anything but plain L1: the optimised value and the masked MAE come out of one fused call (loss.MaskedLoss.last_mae)
+        self._loss_module = None if plain_l1 else MaskedLoss(kind, delta, slope_weight, grad_sync=self.grad_sync)
+        self._last_mae = None
         # host -> device staging of the next batch under the current step (DevicePrefetcher); 0 = the copies ride the compute
         # stream in front of the forward, as in r04
         self.prefetch_batches = int(_get(args, "prefetch_batches", 1))
@@ -289,7 +295,8 @@ class Trainer:
 
     # ------------------------------------------------------------------------------------------
     def _loss_on_device(self, batch, train: bool):
-        """forward (+ backward when training); returns the 0-dim device loss (no host sync)."""
+        """forward (+ backward when training); returns the 0-dim device loss (no host sync) and leaves the batch's masked MAE
+        in `_last_mae` (plain L1: the loss itself)."""
         x, y, loss_mask = self._extract_inputs_outputs_loss_masks(batch)
         x = x.to(self.device, non_blocking=True)
         y = y.to(self.device, non_blocking=True)
@@ -299,31 +306,53 @@ class Trainer:
         if train:
             self.model.train()
             y_pred = self.model(x)
-            loss = masked_l1_loss(y_pred, y, loss_mask, mean, std, grad_sync=self.grad_sync)
+            loss = self._criterion_on_device(y_pred, y, loss_mask, mean, std)
             loss.backward()
         else:
             self.model.eval()
             with torch.no_grad():
                 y_pred = self.model(x)
-                loss = masked_l1_loss(y_pred, y, loss_mask, mean, std, grad_sync=self.grad_sync)
+                loss = self._criterion_on_device(y_pred, y, loss_mask, mean, std)
         return loss.detach()
+
+    def _criterion_on_device(self, y_pred, y, loss_mask, mean, std):
+        if self._loss_module is None:
+            loss = masked_l1_loss(y_pred, y, loss_mask, mean, std, grad_sync=self.grad_sync)
+            self._last_mae = loss.detach()
+        else:
+            loss = self._loss_module(y_pred, y, loss_mask, mean, std)
+            self._last_mae = self._loss_module.last_mae
+        return loss
 
     def inference_one_batch(self, batch, phase):
         assert phase in ["train", "val"]
         loss = self._loss_on_device(batch, phase == "train")
-        return {"MAE_metric": float(loss.item())}
+        if self._loss_module is None:
+            return {"MAE_metric": float(loss.item())}
+        out = {"MAE_metric": float(self._last_mae.item())}
+        if phase == "train":
+            out["loss"] = float(loss.item())
+        return out
 
     @staticmethod
     def stats_dict():
         return {"MAE_metric": 0.0}
 
-    def stats_meter(self):
-        return {k: AverageMeter() for k in self.stats_dict()}
+    def stats_meter(self, phase="val"):
+        """MAE_metric; a train phase that optimises something other than plain L1 also meters that value as `loss`."""
+        meters = {k: AverageMeter() for k in self.stats_dict()}
+        if phase == "train" and self._loss_module is not None:
+            meters["loss"] = AverageMeter()
+        return meters
 
     def inference_one_epoch(self, epoch, phase):
         assert phase in ["train", "val"]
-        meters = self.stats_meter()
-        dev = _DeviceMeter()
+        meters = self.stats_meter(phase)
+        dev = {k: _DeviceMeter() for k in meters}
+
+        def flush():
+            for k, d in dev.items():
+                d.flush_into(meters[k])
         loader = self.loader[phase]
         num_iter = len(loader)
         if self.prefetch_batches > 0 and self.device.type == "cuda":
@@ -336,10 +365,10 @@ class Trainer:
             if self._graphed is None or self._graphed.model is not self.model or self._graphed.optimizer is not self.optimizer:
                 if self.launch_plan:
                     from .plan import PlannedTrainStep
-                    self._graphed = PlannedTrainStep(self.model, self.optimizer)
+                    self._graphed = PlannedTrainStep(self.model, self.optimizer, loss=self._loss_module)
                 else:
                     from .graph import GraphedTrainStep
-                    self._graphed = GraphedTrainStep(self.model, self.optimizer)
+                    self._graphed = GraphedTrainStep(self.model, self.optimizer, loss=self._loss_module)
             graphed = self._graphed
             self.model.train()
         for c_iter, batch in enumerate(loader):
@@ -347,17 +376,21 @@ class Trainer:
                 x, y, loss_mask = self._extract_inputs_outputs_loss_masks(batch)
                 to = lambda t, dt=None: t.to(self.device, dtype=dt, non_blocking=True)      # noqa: E731
                 # .clone(): after a replay the loss is the graph's own output buffer, rewritten by the next one
-                dev.add(graphed(to(x), to(y), to(loss_mask), to(torch.flatten(batch["dsm_mean"]), torch.float32),
-                                to(torch.flatten(batch["dsm_std"]), torch.float32)).clone())
+                loss = graphed(to(x), to(y), to(loss_mask), to(torch.flatten(batch["dsm_mean"]), torch.float32),
+                               to(torch.flatten(batch["dsm_std"]), torch.float32)).clone()
+                self._last_mae = loss if self._loss_module is None else graphed.mae.clone()
             else:
-                dev.add(self._loss_on_device(batch, phase == "train"))
+                loss = self._loss_on_device(batch, phase == "train")
+            dev["MAE_metric"].add(self._last_mae)
+            if "loss" in dev:
+                dev["loss"].add(loss)
             if phase == "train":
                 if graphed is None:
                     self.optimizer.step()
                     for p in params:
                         p.grad = None
                 if (c_iter + 1) % self.freq_average_train_loss == 0:
-                    dev.flush_into(meters["MAE_metric"])
+                    flush()
                     curr_iter = num_iter * epoch + (c_iter + 1)
                     message = f"{phase}:\tEpoch: {epoch} [{c_iter + 1}/{num_iter}]\t"
                     for key, value in meters.items():
@@ -366,7 +399,7 @@ class Trainer:
                         value.reset()
                     self.logger.info(message)
                     self.writer.add_scalar("train/learning_rate", self._get_lr(), curr_iter)
-        dev.flush_into(meters["MAE_metric"])
+        flush()
         return meters
 
     def train(self):

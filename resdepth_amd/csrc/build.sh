@@ -18,22 +18,28 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 #      0.3-0.6 % end to end (r03 interleaved A/B, profiles/r03_notes.md).
 BASE="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -fno-slp-vectorize -Wall -Wno-unused-result $RD_EXTRA_FLAGS"
 FLAGS="$BASE -mllvm -amdgpu-mfma-vgpr-form"
-# RD_CLEAN=1 (what __graft_entry__.build() sets): drop every object first, so "does it build" compiles all nine translation
+# RD_CLEAN=1 (what __graft_entry__.build() sets): drop every object first, so "does it build" compiles all ten translation
 # units from source instead of re-linking whatever obj/ holds
 [ -n "$RD_CLEAN" ] && rm -rf "$OBJ"
 mkdir -p "$OBJ"
+# the translation units, and the headers whose change rebuilds every object
+UNITS="rd_runtime rd_igemm rd_convt rd_wgrad_strip rd_elementwise rd_tiles rd_edge_conv rd_stats rd_trainset rd_loss"
+INC="$HERE/../../include"
+HEADERS=("$HERE/rd_common.h" "$HERE/rd_mfma_dev.h" "$HERE/rd_nt.h" "$HERE/rd_tile_dev.h" "$INC/resdepth_hip.h"
+         "$INC/resdepth_hip_tta.h" "$INC/resdepth_hip_pairs.h" "$INC/resdepth_hip_eval.h" "$INC/resdepth_hip_loss.h")
 pids=()
-for f in rd_runtime rd_igemm rd_convt rd_wgrad_strip rd_elementwise rd_edge_conv rd_stats rd_trainset rd_loss; do
-  if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ "$HERE/rd_common.h" -nt "$OBJ/$f.o" ] \
-     || [ "$HERE/rd_mfma_dev.h" -nt "$OBJ/$f.o" ] || [ "$HERE/rd_nt.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/resdepth_hip.h" -nt "$OBJ/$f.o" ] \
-     || [ "$HERE/../../include/resdepth_hip_tta.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/resdepth_hip_pairs.h" -nt "$OBJ/$f.o" ] \
-     || [ "$HERE/../../include/resdepth_hip_eval.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/resdepth_hip_loss.h" -nt "$OBJ/$f.o" ]; then
+objs=()
+for f in $UNITS; do
+  objs+=("$OBJ/$f.o")
+  stale=; [ -f "$OBJ/$f.o" ] || stale=1
+  for d in "$HERE/$f.hip" "${HEADERS[@]}"; do [ "$d" -nt "$OBJ/$f.o" ] && stale=1; done
+  if [ -n "$stale" ]; then
     F="$FLAGS"; [ $f = rd_wgrad_strip ] && F="$BASE"     # 144 accumulator registers: AGPR-form MFMA (see the file header)
     $HIPCC $F -c "$HERE/$f.hip" -o "$OBJ/$f.o" &
     pids+=($!)
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ"/rd_runtime.o "$OBJ"/rd_igemm.o "$OBJ"/rd_convt.o "$OBJ"/rd_wgrad_strip.o "$OBJ"/rd_elementwise.o "$OBJ"/rd_edge_conv.o "$OBJ"/rd_stats.o "$OBJ"/rd_trainset.o "$OBJ"/rd_loss.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "${objs[@]}"
 [ -n "$RD_SKIP_ISA_CHECK" ] || bash "$HERE/../../scripts/check_isa.sh" "$OUT"
 echo "built $OUT"

@@ -182,6 +182,12 @@ inline int ilog2_exact(int v) {
 }
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// a grid of g blocks, at least 1 and at most cap (grid-stride kernels)
+inline int grid_cap(long g, int cap) {
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
 
 // Division of 0 <= n < 2^31 by a launch-time constant d (image width, pixels per image) as one v_mul_hi + shift:
 // q = (n * mul) >> (32 + sh) with mul = ceil(2^(31+s) / d), s = ceil(log2 d), sh = s - 1  (error term n * e < 2^(31+s)

@@ -12,6 +12,7 @@
 // error of the means.  What a piece is depends on the patch / the rectangle alone, never on the launch: results are
 // independent of n, of the place in the list and of the grid.
 #include "rd_common.h"
+#include "rd_tile_dev.h"
 
 namespace rd {
 
@@ -26,11 +27,6 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh) {
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-__device__ __forceinline__ float4 ld4v(const float* __restrict__ p, bool vec) {
-    if (vec) return *reinterpret_cast<const float4*>(p);
-    return make_float4(p[0], p[1], p[2], p[3]);
 }
 
 // pieces first .. first + n_pieces - 1 of `ws`, each (count, sum, M2 about the piece's mean) -> (count, mean, M2), in that order
@@ -68,7 +64,7 @@ __global__ __launch_bounds__(256) void patch_moments_slab(const float* __restric
         int r = t / TQ, q = t - r * TQ;                // (row, quad) of element t; + 256 per step without a division
         const int dr = 256 / TQ, dq = 256 - dr * TQ;
         for (; r < rows; r += dr) {
-            const float4 v = ld4v(plane + (long)(y0 + r0 + r) * W + x0 + q * 4, vec);
+            const float4 v = ld4(plane + (long)(y0 + r0 + r) * W + x0 + q * 4, vec);
             if (!use_nodata || v.x != nodata) { s += v.x; c += 1.0; }
             if (!use_nodata || v.y != nodata) { s += v.y; c += 1.0; }
             if (!use_nodata || v.z != nodata) { s += v.z; c += 1.0; }
@@ -84,7 +80,7 @@ __global__ __launch_bounds__(256) void patch_moments_slab(const float* __restric
         int r = t / TQ, q = t - r * TQ;
         const int dr = 256 / TQ, dq = 256 - dr * TQ;
         for (; r < rows; r += dr) {
-            const float4 v = ld4v(plane + (long)(y0 + r0 + r) * W + x0 + q * 4, vec);
+            const float4 v = ld4(plane + (long)(y0 + r0 + r) * W + x0 + q * 4, vec);
             double d;
             if (!use_nodata || v.x != nodata) { d = (double)v.x - mean; m2 += d * d; }
             if (!use_nodata || v.y != nodata) { d = (double)v.y - mean; m2 += d * d; }
@@ -218,9 +214,9 @@ __device__ __forceinline__ TrainSample train_sample(const int* __restrict__ samp
     return g;
 }
 
-// sums[i] = (DSM sum, DSM count, ortho sum, ortho count) in the order of patch_sums_kernel (rd_elementwise.hip): thread t adds
-// the elements t, t + 256, ... of the patch, plane after plane, then the same 256-leaf tree -- what GpuPatchSampler.sample's
-// means are made of, so a sample assembled here or there has the same bits.  blockIdx.y: 0 = DSM, 1 = orthos.
+// sums[i] = (DSM sum, DSM count, ortho sum, ortho count) in the order of patch_sums_kernel (rd_tiles.hip): thread t adds the
+// elements t, t + 256, ... of the patch, plane after plane, then the same tree_sum_256 -- what GpuPatchSampler.sample's means
+// are made of, so a sample assembled here or there has the same bits.  blockIdx.y: 0 = DSM, 1 = orthos.
 __global__ __launch_bounds__(256) void train_patch_sums(const rd_train_raster* __restrict__ rasters, int n_rasters,
                                                         const int* __restrict__ samples, int n, int V, int T,
                                                         double* __restrict__ sums) {
@@ -254,16 +250,7 @@ __global__ __launch_bounds__(256) void train_patch_sums(const rd_train_raster* _
         }
     }
     if (!want) return;                                   // uniform over the block
-    red[t] = s;
-    red[256 + t] = c;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) {
-            red[t] += red[t + off];
-            red[256 + t] += red[256 + t + off];
-        }
-        __syncthreads();
-    }
+    tree_sum_256<2>({s, c}, red);
     if (t == 0) {
         sums[(long)i * 4 + which * 2] = red[0];
         sums[(long)i * 4 + which * 2 + 1] = red[256];
@@ -271,7 +258,7 @@ __global__ __launch_bounds__(256) void train_patch_sums(const rd_train_raster* _
 }
 
 // grid (sample, output plane, row block): a lane writes four adjacent output pixels (16-byte stores, 4-byte mask stores) and
-// gathers their sources through the inverse of rot90(k) -> flipud -> fliplr; an unrotated, unmirrored row is one 16-byte load
+// gathers their sources through aug_src; a row that is neither rotated nor mirrored left-right is one 16-byte load
 // aug & RD_TRAIN_AUG_BOX: the mask is cut to the sample's box (columns RD_TRAIN_SAMPLE_INTS + V .. + 3), the 'val' samples of
 // DsmOrthoDataset._get_dsm_loss_mask (lib/DsmOrthoDataset.py:434-470); an unflagged sample never touches those columns
 __global__ __launch_bounds__(256) void train_patch_write(const rd_train_raster* __restrict__ rasters, int n_rasters,
@@ -312,9 +299,9 @@ __global__ __launch_bounds__(256) void train_patch_write(const rd_train_raster* 
         src += (long)g.y * W + g.x;
     }
     dst = is_target ? target + (long)i * T * T : input + ((long)i * C + p) * T * T;
-    const int a = g.aug, k = a & 3;
-    const bool fv = (a & 4) != 0, fh = (a & 8) != 0;
-    const bool vec = ok && k == 0 && !fh && (W & 3) == 0 && ((uintptr_t)src & 15) == 0;      // every row of the patch 16-B aligned
+    const int a = g.aug;
+    // k == 0 (bits 0-1) and no left-right mirror (bit 3), every row of the patch 16-B aligned
+    const bool vec = ok && (a & 11) == 0 && (W & 3) == 0 && ((uintptr_t)src & 15) == 0;
     const int TQ = T / 4, r0 = rb * rows_per_block, r1 = min(T, r0 + rows_per_block);
     // the mask's box in output-tile coordinates (inclusive): the whole tile, or the RD_TRAIN_AUG_BOX sample's own columns -- read
     // by the target plane of a flagged sample only; a box that is not inside the tile is empty
@@ -331,41 +318,24 @@ __global__ __launch_bounds__(256) void train_patch_write(const rd_train_raster* 
         const int r = r0 + e / TQ, c = (e % TQ) * 4;
         float4 v = make_float4(qnan, qnan, qnan, qnan), o = v;
         if (ok) {
-            const int rr = fv ? T - 1 - r : r;
-            if (vec) {
-                v = *reinterpret_cast<const float4*>(src + (long)rr * W + c);
+            if (vec) {       // k == 0, no left-right mirror: the source row is r or its up-down mirror, columns as they are
+                v = *reinterpret_cast<const float4*>(src + (long)((a & 4) ? T - 1 - r : r) * W + c);
             } else {
                 float xs[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int c1 = fh ? T - 1 - (c + j) : c + j;
                     int sr, sc;
-                    if (k == 0) { sr = rr; sc = c1; }
-                    else if (k == 1) { sr = c1; sc = T - 1 - rr; }
-                    else if (k == 2) { sr = T - 1 - rr; sc = T - 1 - c1; }
-                    else { sr = T - 1 - c1; sc = rr; }
+                    aug_src(a, T, r, c + j, sr, sc);
                     xs[j] = src[(long)sr * W + sc];
                 }
                 v = make_float4(xs[0], xs[1], xs[2], xs[3]);
             }
-            o = v;
-            if (mode) {
-                o.x = __fdiv_rn(__fsub_rn(v.x, mean), sdv);
-                o.y = __fdiv_rn(__fsub_rn(v.y, mean), sdv);
-                o.z = __fdiv_rn(__fsub_rn(v.z, mean), sdv);
-                o.w = __fdiv_rn(__fsub_rn(v.w, mean), sdv);
-            }
+            o = mode ? norm4(v, mean, sdv) : v;
         }
         *reinterpret_cast<float4*>(dst + (long)r * T + c) = o;
-        if (is_target) {
-            const bool in_rows = ok && r >= by0 && r <= by1;
-            uchar4 m;
-            m.x = in_rows && c >= bx0 && c <= bx1 && v.x != 0.f && v.x != nodata;
-            m.y = in_rows && c + 1 >= bx0 && c + 1 <= bx1 && v.y != 0.f && v.y != nodata;
-            m.z = in_rows && c + 2 >= bx0 && c + 2 <= bx1 && v.z != 0.f && v.z != nodata;
-            m.w = in_rows && c + 3 >= bx0 && c + 3 <= bx1 && v.w != 0.f && v.w != nodata;
-            *reinterpret_cast<uchar4*>(mask + (long)i * T * T + (long)r * T + c) = m;
-        }
+        if (is_target)
+            *reinterpret_cast<uchar4*>(mask + (long)i * T * T + (long)r * T + c) =
+                mask4(v, ok && r >= by0 && r <= by1, c, bx0, bx1, nodata);
     }
 }
 
@@ -479,7 +449,7 @@ int rd_assemble_train_patches(const rd_train_raster* rasters, int n_rasters, con
         RD_LAUNCH_CHECK("train_patch_sums");
     }
     const int planes_out = dsm_channel + views + (target ? 1 : 0);
-    const int rows_per_block = 4096 / tile < 1 ? 1 : (4096 / tile > tile ? tile : 4096 / tile);
+    const int rows_per_block = tile_rows_per_block(tile);
     ProfScope ps((hipStream_t)s, "train_patch_write", 0, px * (8.0 * planes_out + (target ? 1.0 : 0.0)));
     RD_LAUNCH(train_patch_write, dim3(n, planes_out, cdiv(tile, rows_per_block)), dim3(256), 0, (hipStream_t)s, rasters, n_rasters,
               samples, n, views, dsm_channel, tile, (const double*)sums, rows_per_block, input, target, mask, dsm_mean_out);

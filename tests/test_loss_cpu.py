@@ -146,6 +146,9 @@ def test_side_header_signatures_constants_and_version():
 
 def test_the_new_unit_is_built_and_launches_through_rd_launch():
     build = open(os.path.join(ROOT, "resdepth_amd", "csrc", "build.sh")).read()
-    assert re.search(r"for f in [^;]*\brd_loss\b", build) and '"$OBJ"/rd_loss.o' in build
+    # one list of translation units feeds the compile loop and, through the loop's objs array, the link line
+    units = re.search(r'^UNITS="([^"]*)"$', build, re.M).group(1).split()
+    assert "rd_loss" in units and "for f in $UNITS; do" in build and 'objs+=("$OBJ/$f.o")' in build
+    assert re.search(r'^\$HIPCC [^\n]*-shared [^\n]*-o "\$OUT" "\$\{objs\[@\]\}"$', build, re.M)
     src = open(os.path.join(ROOT, "resdepth_amd", "csrc", "rd_loss.hip")).read()
     assert "RD_LAUNCH(" in src and "hipLaunchKernelGGL" not in src and "<<<" not in src and "atomicAdd" not in src

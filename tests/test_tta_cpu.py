@@ -77,7 +77,7 @@ def test_numpy_restatement_is_torch_rot90_flipud_fliplr(code):
     assert np.array_equal(inv, _torch_undo(torch.from_numpy(x), code).numpy(), equal_nan=True)
     assert np.array_equal(tiling.tta_undo(fwd, code), x, equal_nan=True)
     assert np.array_equal(tiling.tta_apply(inv, code), x, equal_nan=True)
-    # the index form the kernels use (csrc/rd_elementwise.hip: aug_src): oriented (r, c) shows plain (sr, sc)
+    # the index form the kernels use (csrc/rd_tile_dev.h: aug_src): oriented (r, c) shows plain (sr, sc)
     T, k = 8, code & 3
     for r, c in [(0, 0), (1, 5), (7, 2)]:
         c1, r1 = (T - 1 - c if code & 8 else c), (T - 1 - r if code & 4 else r)

@@ -647,4 +647,5 @@ int rd_prof_collect(rd_prof_entry* out, int max_entries); /* returns number of c
 #include "resdepth_hip_pairs.h" /* all image pairs in one sweep: the blend into planes and the per-pixel fusion */
 #include "resdepth_hip_eval.h" /* scoring the planes of a pair sweep: classification of P planes, statistics pooled over planes */
 #include "resdepth_hip_loss.h" /* masked L2 / Huber / slope-consistency training losses and the MAE beside them */
+#include "resdepth_hip_optim.h" /* global norm and non-finite count of the flat gradient */
 #endif /* RESDEPTH_HIP_H */

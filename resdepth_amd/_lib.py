@@ -183,6 +183,13 @@ SIGNATURES_LOSS = {
 # the constants of that header
 LOSS_KINDS = {"l1": 0, "l2": 1, "huber": 2}
 LOSS_STRIP_ROWS, LOSS_STRIP_COLS, LOSS_MAX_BLOCKS = 32, 64, 1024
+# include/resdepth_hip_optim.h (statistics of the flat gradient: global norm, non-finite count), one to one as above
+SIGNATURES_OPTIM = {
+    "rd_grad_norm_ws_bytes": (SZ, [LL]),
+    "rd_grad_norm": (I, [P, LL, P, P, SZ, P]),
+}
+# the constants of that header
+GNORM_BLOCK, GNORM_VEC, GNORM_MAX_BLOCKS = 256, 4, 1024
 
 
 class ProfEntry(C.Structure):
@@ -204,7 +211,7 @@ def load():
                 "there is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
-                + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()):
+                + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

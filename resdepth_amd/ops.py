@@ -759,6 +759,18 @@ def adam_step_dev(p, g, m, v, scalars_dev):
     check(load().rd_adam_step_dev(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(scalars_dev), stream_ptr()), "adam_step_dev")
 
 
+def grad_norm(g, stats=None, ws=None):
+    """-> stats [2] float64 on device: sum of squares of the finite elements of the flat gradient `g`, number of non-finite
+    elements (include/resdepth_hip_optim.h); the global norm is stats[0].sqrt().  Two launches, no sync.  ws: a scratch of the caller's own (uint8, at least
+    rd_grad_norm_ws_bytes(numel)), else the stream's shared one."""
+    if stats is None:
+        stats = torch.empty(2, device=g.device, dtype=torch.float64)
+    if ws is None:
+        ws = workspace(load().rd_grad_norm_ws_bytes(g.numel()), g.device)
+    check(load().rd_grad_norm(ptr(g), g.numel(), ptr(stats), ws.data_ptr(), ws.numel(), stream_ptr()), "grad_norm")
+    return stats
+
+
 def sgd_step(p, g, buf, lr, weight_decay, momentum=0.0, dampening=0.0, nesterov=False, first_step=False, grad_scale=1.0):
     check(load().rd_sgd_step(ptr(p), ptr(g), ptr(buf), p.numel(), lr, weight_decay, momentum, dampening,
                              1 if nesterov else 0, 1 if first_step else 0, grad_scale, stream_ptr()), "sgd_step")

@@ -67,6 +67,8 @@ class FusedAdam(torch.optim.Optimizer):
             if flat is None or pr is None or gr is None or pr[0] != flat[0] or gr[1] != flat[1].numel() or \
                     not self._same_layout(params, pr, gr):
                 return False
+            if len({float(self.state[p]["step"]) for p in params}) != 1:
+                return False               # the scalar block holds ONE pair of bias corrections (see _step_group)
             dev = params[0].device
             groups.append(dict(gi=gi, t=float(self.state[params[0]]["step"]), dev=torch.zeros(8, device=dev, dtype=torch.float32),
                                ring=torch.zeros(self._RING, 8, dtype=torch.float32).pin_memory(), events=[None] * self._RING, slot=0))
@@ -164,12 +166,7 @@ class FusedAdam(torch.optim.Optimizer):
                     st.setdefault("step", torch.tensor(0.0))
                 self._flat_state[gi] = (fr[0], m, v)
             return self._flat_state[gi]
-        for p in params:
-            st = self.state[p]
-            if "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p.data)
-                st["exp_avg_sq"] = torch.zeros_like(p.data)
+        self._ensure_state_per_tensor(params)
         return None
 
     @torch.no_grad()
@@ -211,21 +208,21 @@ class FusedAdam(torch.optim.Optimizer):
         else:
             gr = None
             self._ensure_state_per_tensor(active)
-        # step counter (python float tensors like torch.optim.Adam's default path)
+        # step counter (python float tensors like torch.optim.Adam's default path): one per parameter, and a parameter whose
+        # gradient was None for some steps lags behind the others
         for p in active:
             self.state[p]["step"] += 1
         if not active:
             return
-        t = float(self.state[active[0]]["step"])
-        bc1 = 1.0 - b1 ** t
-        bc2 = 1.0 - b2 ** t
-        step_size = lr / bc1
-        bc2_sqrt = math.sqrt(bc2)
+        counts = {float(self.state[p]["step"]) for p in active}
         pr = self._flat_range([p.data for p in params]) if flat is not None and gr is not None else None
-        if pr is not None and gr[1] == flat[1].numel() and pr[0] == flat[0] and self._same_layout(params, pr, gr):
+        # one launch only when one pair of bias corrections serves the whole group (the counters are CPU tensors: no sync)
+        if len(counts) == 1 and pr is not None and gr[1] == flat[1].numel() and pr[0] == flat[0] and \
+                self._same_layout(params, pr, gr):
             total = gr[1]
             pflat = _as_flat(params[pr[2]].data, total)
             gflat = _as_flat(params[gr[2]].grad, total)
+            step_size, bc2_sqrt = _bias_corrections(lr, b1, b2, counts.pop())
             ops.adam_step(pflat, gflat, flat[1], flat[2], b1, b2, eps, wd, step_size, bc2_sqrt, self.grad_scale)
             # every parameter pointer of the group, not only the flat buffer's first: a model's pack key reads the generations
             # of ITS OWN parameters, and one group may span several models' (contiguously allocated) flat buffers
@@ -234,10 +231,18 @@ class FusedAdam(torch.optim.Optimizer):
         else:
             for p in active:
                 st = self.state[p]
-                g = p.grad.contiguous()
-                ops.adam_step(p.data.view(-1) if p.data.is_contiguous() else p.data, g.view(-1),
-                              st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), b1, b2, eps, wd, step_size,
-                              bc2_sqrt, self.grad_scale)
+                for k in ("exp_avg", "exp_avg_sq"):          # e.g. loaded from a torch.optim.Adam that kept the parameter's strides
+                    if not st[k].is_contiguous():
+                        st[k] = st[k].contiguous()
+                # a dense but permuted parameter (a transposed view, a channels_last weight): its memory order is not the
+                # logical order of the gradient and the moments, so the launch steps a contiguous copy
+                in_order = p.data.is_contiguous()
+                pc = p.data if in_order else p.data.contiguous()
+                step_size, bc2_sqrt = _bias_corrections(lr, b1, b2, float(st["step"]))
+                ops.adam_step(pc.view(-1), p.grad.contiguous().view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
+                              b1, b2, eps, wd, step_size, bc2_sqrt, self.grad_scale)
+                if not in_order:
+                    p.data.copy_(pc)
             # `.data` writes do not bump Parameter._version: tell the packed-weight caches of the models that own these
             # tensors (UNet._current_pack_key reads the generation of every parameter pointer) -- and only those
             for p in active:
@@ -248,8 +253,8 @@ class FusedAdam(torch.optim.Optimizer):
             st = self.state[p]
             if "exp_avg" not in st:
                 st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p.data)
-                st["exp_avg_sq"] = torch.zeros_like(p.data)
+                st["exp_avg"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
 
 
 class FusedSGD(torch.optim.Optimizer):
@@ -338,10 +343,14 @@ class FusedSGD(torch.optim.Optimizer):
                 if st.get("momentum_buffer") is None:
                     st["momentum_buffer"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
                     first = True
+                elif not st["momentum_buffer"].is_contiguous():      # loaded from a torch.optim.SGD that kept the strides
+                    st["momentum_buffer"] = st["momentum_buffer"].contiguous()
                 buf = st["momentum_buffer"].view(-1)
-            g = p.grad.contiguous()
-            ops.sgd_step(p.data.view(-1) if p.data.is_contiguous() else p.data, g.view(-1), buf, lr, wd, mom, damp, nest,
-                         first, self.grad_scale)
+            in_order = p.data.is_contiguous()         # else a contiguous copy is stepped (see FusedAdam._step_group)
+            pc = p.data if in_order else p.data.contiguous()
+            ops.sgd_step(pc.view(-1), p.grad.contiguous().view(-1), buf, lr, wd, mom, damp, nest, first, self.grad_scale)
+            if not in_order:
+                p.data.copy_(pc)
             _lib.bump_param_generation(p.data_ptr())
 
 
@@ -360,6 +369,11 @@ def get_optimizer(cfg, model, logger=None):
     else:
         print(f"ERROR: {msg}")
     raise UnboundLocalError("local variable 'optimizer' referenced before assignment")
+
+
+def _bias_corrections(lr, b1, b2, t):
+    """(lr / (1 - b1^t), sqrt(1 - b2^t)) of step count t, as torch.optim.Adam computes them on the host."""
+    return lr / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)
 
 
 def _as_flat(first: torch.Tensor, total: int) -> torch.Tensor:

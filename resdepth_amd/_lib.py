@@ -190,6 +190,15 @@ SIGNATURES_OPTIM = {
 }
 # the constants of that header
 GNORM_BLOCK, GNORM_VEC, GNORM_MAX_BLOCKS = 256, 4, 1024
+# include/resdepth_hip_dist.h (quantiles and within-tolerance shares of the statistics sets), one to one as above
+SIGNATURES_DIST = {
+    "rd_residual_dist_sets_ws_bytes": (SZ, [LL, I, I, I]),
+    "rd_residual_dist_sets": (I, [P, P, P, LL, P, P, P, I, P, P, I, P, I, P, P, SZ, P]),
+    "rd_residual_dist_pooled_ws_bytes": (SZ, [LL, I, I, I]),
+    "rd_residual_dist_pooled": (I, [P, LL, I, I, I, P, P, LL, P, P, I, P, P, I, P, I, P, P, SZ, P]),
+}
+# the constants of that header
+DIST_MAX_Q, DIST_MAX_T = 8, 8
 
 
 class ProfEntry(C.Structure):
@@ -211,7 +220,8 @@ def load():
                 "there is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
-                + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()):
+                + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()) \
+                + list(SIGNATURES_DIST.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

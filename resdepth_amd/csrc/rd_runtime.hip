@@ -259,7 +259,7 @@ static void drain_locked() {
 
 extern "C" {
 
-int rd_version(void) { return 115; }      // 101 (r04): rd_set_splitk_workspace keyed by (device, stream); 102 (r05): rd_host_register; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next, rd_amax, packed operands carry both split forms; 106: rd_plan_*; 107: rd_quant_next_img (per-image magnitude slots); 108: slot word 1 = complement of the smallest non-zero block maximum (three-product guard), a failing call clears the armed slots; 109: rd_assemble_grid_tiles; 110: rd_trainset.hip (patch / region moments, multi-raster training batches); 111: test-time augmentation (rd_assemble_grid_tiles_aug, rd_blend_accumulate_tta); 112: image pairs in one sweep (rd_blend_accumulate_planes, rd_fuse_planes); 113: scoring the planes of a pair sweep (rd_eval_classify_planes, rd_residual_stats_pooled); 114: rd_loss.hip (masked L2 / Huber / slope-consistency losses: rd_masked_loss_partial, rd_masked_loss_finish); 115: rd_optim.hip (global norm and non-finite count of the flat gradient: rd_grad_norm)
+int rd_version(void) { return 116; }      // 101 (r04): rd_set_splitk_workspace keyed by (device, stream); 102 (r05): rd_host_register; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next, rd_amax, packed operands carry both split forms; 106: rd_plan_*; 107: rd_quant_next_img (per-image magnitude slots); 108: slot word 1 = complement of the smallest non-zero block maximum (three-product guard), a failing call clears the armed slots; 109: rd_assemble_grid_tiles; 110: rd_trainset.hip (patch / region moments, multi-raster training batches); 111: test-time augmentation (rd_assemble_grid_tiles_aug, rd_blend_accumulate_tta); 112: image pairs in one sweep (rd_blend_accumulate_planes, rd_fuse_planes); 113: scoring the planes of a pair sweep (rd_eval_classify_planes, rd_residual_stats_pooled); 114: rd_loss.hip (masked L2 / Huber / slope-consistency losses: rd_masked_loss_partial, rd_masked_loss_finish); 115: rd_optim.hip (global norm and non-finite count of the flat gradient: rd_grad_norm); 116: quantiles and within-tolerance shares of the statistics sets (rd_residual_dist_sets, rd_residual_dist_pooled)
 
 const char* rd_last_error_string(void) { return rd::g_err; }
 

@@ -24,16 +24,28 @@ def _stats(raster, gt, mask, nodata, thr, dev):
     return out
 
 
-def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=None, device="cuda"):
+def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=None, device="cuda", *, abs_quantiles=None,
+                   quantiles=None, within=None):
     """raster: refined DSM (any float dtype, e.g. the float64 output of predict_linear_blend), raster_gt: reference DSM,
     mask_gt: optional boolean validity mask.  -> dict as lib/evaluation.py:get_statistics (incl. 'truncated' sub-dict
-    when residual_threshold is given)."""
+    when residual_threshold is given).  abs_quantiles / quantiles / within: see evaluate_statistics."""
     dev = _device(device, "resdepth_amd.evaluation.get_statistics")
+    dist = _dist_options(abs_quantiles, quantiles, within)
     r, g = _on(raster, dev, torch.float64), _on(raster_gt, dev, torch.float32)
     m = None if mask_gt is None else _on(mask_gt, dev).to(torch.uint8).contiguous()
     with torch.cuda.device(r.device):              # raw launches go to the current device's stream
         full = _stats(r, g, m, nodata, None, r.device)
         trunc = _stats(r, g, m, nodata, residual_threshold, r.device) if residual_threshold else None
+        if dist is not None:
+            # the sets form over the residual and validity of residual_kernel (d = a - (double)g; valid = both != nodata,
+            # under the mask), built here; the truncated set is its second set
+            gd = g.to(torch.float64)
+            ok = (r != nodata) & (gd != nodata)
+            if m is not None:
+                ok &= m != 0
+            sets = [(0, 1, None)] + ([(0, 1, residual_threshold)] if residual_threshold else [])
+            drows = torch.empty((len(sets), dist.width), dtype=torch.float64, device=r.device)
+            _queue_dist_sets((r - gd).reshape(-1), None, ok.to(torch.uint8).reshape(-1), sets, dist, drows)
     vals = full.cpu().tolist()
     stats = {"truncation": bool(residual_threshold)}
     stats.update(dict(zip(_KEYS, vals)))
@@ -41,6 +53,11 @@ def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=N
         tv = trunc.cpu().tolist()
         stats["truncated"] = {"count_total": tv[0], "threshold": residual_threshold, "MAE": tv[3], "RMSE": tv[4],
                               "absolute_median": tv[5], "median": tv[6], "NMAD": tv[7]}
+    if dist is not None:
+        drows = drows.cpu().numpy()
+        dist.fill(stats, drows[0])
+        if trunc is not None:
+            dist.fill(stats["truncated"], drows[1])
     return stats
 
 
@@ -150,33 +167,105 @@ def _set_arrays(sets):
     return (need_a, thr_a) if len(sets[0]) == 2 else (need_a, thr_a, (ctypes.c_int * ns)(*[s[0] for s in sets]))
 
 
-def _run_sets(src0, src1, cls, sets, dev):
-    """sets: [(source, need bits, threshold or None)] -> host float64 array [len(sets), 8] (rd_residual_stats_sets)."""
+# ---- error quantiles and within-tolerance shares (include/resdepth_hip_dist.h) -------------------------------------------
+LE = (0.68, 0.90, 0.95)                               # the usual linear-error levels: abs_quantiles=LE gives LE68, LE90, LE95
+MAX_Q = MAX_T = 8                                     # RD_DIST_MAX_Q, RD_DIST_MAX_T
+
+
+class _Dist:
+    """The quantile / share options of one call: the ctypes arrays of rd_residual_dist_*, the width of an output row
+    (count, quantiles, shares) and the way from such a row into a statistics dict."""
+
+    def __init__(self, abs_q, q, within):
+        self.abs_q, self.q, self.within = abs_q, q, within
+        levels = [(v, 1) for v in abs_q] + [(v, 0) for v in q]
+        if len(levels) > MAX_Q or len(within) > MAX_T:
+            raise ValueError(f"evaluate: {len(levels)} quantiles (at most {MAX_Q}) and {len(within)} tolerances (at most "
+                             f"{MAX_T}) in one call")
+        for v, _ in levels:
+            if not 0.0 <= v <= 1.0:
+                raise ValueError(f"evaluate: quantile level {v} outside [0, 1]")
+        for t in within:
+            if not 0.0 <= t < float("inf"):
+                raise ValueError(f"evaluate: tolerance {t} must be finite and >= 0")
+        self.n_q, self.n_t = len(levels), len(within)
+        self.width = 1 + self.n_q + self.n_t
+        self.q_a = (ctypes.c_double * max(self.n_q, 1))(*[v for v, _ in levels])
+        self.mode_a = (ctypes.c_int * max(self.n_q, 1))(*[m for _, m in levels])
+        self.tau_a = (ctypes.c_double * max(self.n_t, 1))(*within)
+
+    def fill(self, st, row):
+        """row (count, quantiles, shares) of one set -> the keys of the options that were given"""
+        v = [float(x) for x in row[1:]]
+        na = len(self.abs_q)
+        if self.abs_q:
+            st["abs_quantile"] = dict(zip(self.abs_q, v[:na]))
+        if self.q:
+            st["quantile"] = dict(zip(self.q, v[na:self.n_q]))
+        if self.within:
+            st["within"] = dict(zip(self.within, v[self.n_q:]))
+
+
+def _dist_options(abs_quantiles, quantiles, within):
+    """-> a _Dist, or None when no option is given (the call then does exactly what it did without them)."""
+    abs_q, q, w = (tuple(float(v) for v in (x if x is not None else ())) for x in (abs_quantiles, quantiles, within))
+    return _Dist(abs_q, q, w) if abs_q or q or w else None
+
+
+def _queue_dist_sets(src0, src1, cls, sets, dist, out):
+    """rd_residual_dist_sets over the sets of _run_sets into out [len(sets), dist.width] (device), enqueued only."""
     n, ns = cls.numel(), len(sets)
     lib = load()
     need_a, thr_a, src_a = _set_arrays(sets)
-    out = torch.empty((ns, 8), dtype=torch.float64, device=dev)
+    ws = workspace(lib.rd_residual_dist_sets_ws_bytes(n, ns, dist.n_q, dist.n_t), out.device, slot=4)
+    check(lib.rd_residual_dist_sets(ptr(src0), ptr(src1), ptr(cls), n, src_a, need_a, thr_a, ns, dist.q_a, dist.mode_a,
+                                    dist.n_q, dist.tau_a, dist.n_t, ptr(out), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "residual_dist_sets")
+
+
+def _run_sets(src0, src1, cls, sets, dev, dist=None):
+    """sets: [(source, need bits, threshold or None)] -> host float64 array [len(sets), 8] (rd_residual_stats_sets); with
+    dist, (that, [len(sets), dist.width] of rd_residual_dist_sets): both enqueued, one device buffer, one read-back."""
+    n, ns = cls.numel(), len(sets)
+    lib = load()
+    need_a, thr_a, src_a = _set_arrays(sets)
+    buf = torch.empty(ns * (8 + (dist.width if dist else 0)), dtype=torch.float64, device=dev)
+    out = buf[:ns * 8].view(ns, 8)
     with torch.cuda.device(dev):
         ws = workspace(lib.rd_residual_stats_sets_ws_bytes(n, ns), dev, slot=3)
         check(lib.rd_residual_stats_sets(ptr(src0), ptr(src1), ptr(cls), n, src_a, need_a, thr_a, ns, ptr(out),
                                          ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats_sets")
-        return out.cpu().numpy()
+        if dist is None:
+            return out.cpu().numpy()
+        _queue_dist_sets(src0, src1, cls, sets, dist, buf[ns * 8:].view(ns, dist.width))
+        host = buf.cpu().numpy()
+        return host[:ns * 8].reshape(ns, 8), host[ns * 8:].reshape(ns, dist.width)
 
 
-def _stats_dict(full, trunc, thr):
-    """rows of rd_residual_stats_sets -> the reference's get_statistics dict."""
+def _stats_dict(full, trunc, thr, dist=None, dfull=None, dtrunc=None):
+    """rows of rd_residual_stats_sets [and of rd_residual_dist_sets] -> the reference's get_statistics dict [with the
+    abs_quantile / quantile / within keys of the options given, in the truncated sub-dict too]."""
     st = AttrDict(truncation=bool(thr))
     if thr:
         st.truncated = AttrDict(count_total=float(trunc[0]), threshold=thr, MAE=float(trunc[3]), RMSE=float(trunc[4]),
                                 absolute_median=float(trunc[5]), median=float(trunc[6]), NMAD=float(trunc[7]))
+        if dist is not None:
+            dist.fill(st.truncated, dtrunc)
     st.update(zip(_KEYS, (float(v) for v in full)))
+    if dist is not None:
+        dist.fill(st, dfull)
     return st
 
 
-def _class_stats(rows, classes, thr):
-    """rows [len(classes) * (2 if thr else 1), 8] in class order (full, truncated) -> {class: stats}."""
+def _class_stats(rows, classes, thr, dist=None, drows=None):
+    """rows [len(classes) * (2 if thr else 1), 8] in class order (full, truncated) -> {class: stats}; drows: the rows of the
+    quantile call over the same sets."""
     step = 2 if thr else 1
-    return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr)) for q, c in enumerate(classes))
+    if dist is None:
+        return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr))
+                        for q, c in enumerate(classes))
+    return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr, dist, drows[q * step],
+                                    drows[q * step + 1] if thr else None)) for q, c in enumerate(classes))
 
 
 def _float_raster(x, dev):
@@ -211,7 +300,7 @@ def _eval_inputs(rows, cols, area_defn, mask_gt, mask_building, mask_water, mask
 
 
 def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
-              nodata, dev):
+              nodata, dev, dist=None):
     """-> (stats {'before', 'after'}, r_after, cls, classes) with r_after / cls on the device."""
     pred = _on(prediction, dev, torch.float64)
     init, g = _float_raster(initial, dev), _float_raster(gt, dev)
@@ -233,14 +322,20 @@ def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_w
     thr = residual_threshold
     sets = [(src, valid | CLASS_BITS[c], t) for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)) for c in classes
             for t in ((None, thr) if thr else (None,))]
-    res = _run_sets(r_before, r_after, cls, sets, dev)
     half = len(sets) // 2                              # source-major: the initial DSM's rows, then the refined DSM's
-    stats = AttrDict(before=_class_stats(res[:half], classes, thr), after=_class_stats(res[half:], classes, thr))
+    if dist is None:
+        res = _run_sets(r_before, r_after, cls, sets, dev)
+        stats = AttrDict(before=_class_stats(res[:half], classes, thr), after=_class_stats(res[half:], classes, thr))
+    else:
+        res, dres = _run_sets(r_before, r_after, cls, sets, dev, dist)
+        stats = AttrDict(before=_class_stats(res[:half], classes, thr, dist, dres[:half]),
+                         after=_class_stats(res[half:], classes, thr, dist, dres[half:]))
     return stats, r_after, cls, classes
 
 
 def evaluate_statistics(prediction, initial, gt, area_defn=None, mask_gt=None, mask_building=None, mask_water=None,
-                        mask_forest=None, residual_threshold=None, *, nodata=None, device="cuda"):
+                        mask_forest=None, residual_threshold=None, *, nodata=None, device="cuda", abs_quantiles=None,
+                        quantiles=None, within=None):
     """The statistics of lib/evaluation.py:163-457 evaluate_performance on the GPU: one classification pass, then every
     statistics set (initial / refined DSM x all / building / terrain / terrain without water / terrain without water and
     forest, each with its truncated variant) out of one shared set of radix-select passes.
@@ -248,14 +343,38 @@ def evaluate_statistics(prediction, initial, gt, area_defn=None, mask_gt=None, m
     prediction: refined DSM; initial: initial DSM; gt: ground-truth DSM (numpy arrays or tensors; f32 / f64 DSMs are
     read as given).  nodata: the ground truth's nodata value (None: none).  Masks: arrays / tensors (value 1 = set),
     (values, nodata) tuples or dataset-like objects; water and forest only count with a building mask.
-    -> {'before': {class: stats}, 'after': {class: stats}} in the reference's get_statistics format, attribute access."""
+    -> {'before': {class: stats}, 'after': {class: stats}} in the reference's get_statistics format, attribute access.
+
+    Beyond the reference, three keyword options add what accuracy specifications quote, for every set (the truncated ones
+    too), by one rd_residual_dist_sets call over the same sets -- no sort, nothing but the results read back:
+      abs_quantiles=  levels of |residual| (evaluation.LE = 0.68, 0.90, 0.95 gives LE68, LE90, LE95) -> stats.abs_quantile
+      quantiles=      levels of the signed residual                                                  -> stats.quantile
+      within=         tolerances in metres: the share of pixels with |residual| <= tolerance, 0..1   -> stats.within
+    each a dict keyed by the level / tolerance as given; numpy's `linear` quantile rule (include/resdepth_hip_dist.h); at most
+    8 levels and 8 tolerances.  Without them the dicts and the library calls are exactly what they were."""
     dev = _first_device(prediction, initial, gt, default=device)
     return _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest,
-                     residual_threshold, nodata, dev)[0]
+                     residual_threshold, nodata, dev, _dist_options(abs_quantiles, quantiles, within))[0]
+
+
+def _print_dist(st, logger, prefix=""):
+    """One line per quantile / share present in st, in the block's number format."""
+    name = (lambda text: prefix + text[0].lower() + text[1:]) if prefix else (lambda text: text)
+    lines = []
+    for q, v in st.get("abs_quantile", {}).items():
+        lines.append((name("Linear error LE{:g} (|residual| quantile) [m]:".format(100 * q)), v, "m"))
+    for q, v in st.get("quantile", {}).items():
+        lines.append((name("Residual quantile q={:g} [m]:".format(q)), v, "m"))
+    for tau, v in st.get("within", {}).items():
+        lines.append((name("Share of pixels within {:.2f} m [%]:".format(tau)), 100.0 * v, "%"))
+    for k, (text, v, unit) in enumerate(lines):
+        tabs = "\t" * max(1, 9 - len(text) // 8)             # the value column of the reference's block (tab stop 72)
+        logger.info("{}{}{:10.3f} {}{}".format(text, tabs, v, unit, "\n" if k == len(lines) - 1 else ""))
 
 
 def print_statistics(stats, logger, print_min_max=True):
-    """The report block of lib/evaluation.py:134-160, line for line."""
+    """The report block of lib/evaluation.py:134-160, line for line; after it (and after the truncated block) one line per
+    abs_quantile / quantile / within value, when the statistics carry those keys."""
     if print_min_max:
         logger.info("Maximum residual error [m]:\t\t\t\t\t\t{:10.3f} m".format(stats.diff_max))
         logger.info("Minimum residual error [m]:\t\t\t\t\t\t{:10.3f} m".format(stats.diff_min))
@@ -264,6 +383,7 @@ def print_statistics(stats, logger, print_min_max=True):
     logger.info("Absolute median residual error [m]:\t\t\t\t\t{:10.3f} m".format(stats.absolute_median))
     logger.info("Median residual error [m]:\t\t\t\t\t\t{:10.3f} m".format(stats.median))
     logger.info("Normalized median absolute deviation (NMAD) [m]:\t\t\t{:10.3f} m\n".format(stats.NMAD))
+    _print_dist(stats, logger)
     if stats.truncation:
         t = stats.truncated
         logger.info("Truncated mean absolute residual error (MAE) [m]:\t\t\t{:10.3f} m".format(t.MAE))
@@ -271,6 +391,7 @@ def print_statistics(stats, logger, print_min_max=True):
         logger.info("Truncated absolute median residual error [m]:\t\t\t\t{:10.3f} m".format(t.absolute_median))
         logger.info("Truncated median residual error [m]:\t\t\t\t\t{:10.3f} m".format(t.median))
         logger.info("Truncated normalized median absolute deviation (NMAD) [m]:\t\t{:10.3f} m\n".format(t.NMAD))
+        _print_dist(t, logger, "Truncated ")
 
 
 def _gdal():
@@ -385,14 +506,16 @@ def _write_report(stats, classes, gsd, residual_threshold, logger_stats):
 
 def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logger_root, area_defn=None,
                          path_gt_mask=None, path_building_mask=None, path_water_mask=None, path_forest_mask=None,
-                         logger_stats=None, residual_threshold=None, *, nodata=None, gsd=None, device="cuda"):
+                         logger_stats=None, residual_threshold=None, *, nodata=None, gsd=None, device="cuda",
+                         abs_quantiles=None, quantiles=None, within=None):
     """Drop-in for lib/evaluation.py:163 evaluate_performance: the same report on `logger_stats` and the same return
     value, the attribute dict `residuals.after` of host np.ma.MaskedArrays (class -> residuals of the refined DSM).
 
     The DSMs are arrays / tensors or dataset-like objects (GetRasterBand(1).ReadAsArray(), GetNoDataValue(),
     GetGeoTransform()); for arrays the ground truth's nodata value and the GSD come from `nodata=` / `gsd=`.  Mask
     arguments: arrays (value 1 = set), (values, nodata) tuples, dataset-like objects or paths (paths need osgeo.gdal; a
-    path that does not exist is logged and skipped; a missing ground-truth mask means all ground-truth pixels)."""
+    path that does not exist is logged and skipped; a missing ground-truth mask means all ground-truth pixels).
+    abs_quantiles / quantiles / within (see evaluate_statistics) add their lines to every block of the report."""
     if logger_stats is None:
         logger_stats = _default_stats_logger()
     pred, _ = _raster_arg(raster_prediction, "refined DSM", logger_root)
@@ -403,7 +526,8 @@ def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logge
     dev = _device(device)
     logger_root.info("\tCompute residual errors and statistics before and after the refinement...")
     stats, r_after, cls, classes = _evaluate(pred, init, gt, area_defn, mask_gt, mask_b, mask_w, mask_f,
-                                             residual_threshold, nodata, dev)
+                                             residual_threshold, nodata, dev,
+                                             _dist_options(abs_quantiles, quantiles, within))
     _write_report(stats, classes, gsd, residual_threshold, logger_stats)
 
     data = r_after.cpu().numpy()
@@ -416,10 +540,13 @@ def evaluate_performance(raster_prediction, ds_raster_input, ds_raster_gt, logge
     return residuals
 
 
-def get_statistics_masked(residuals_masked, residual_threshold=None, device="cuda"):
+def get_statistics_masked(residuals_masked, residual_threshold=None, device="cuda", *, abs_quantiles=None, quantiles=None,
+                          within=None):
     """The reference's get_statistics(residuals_masked, residual_threshold) (lib/evaluation.py:50): statistics of the
     unmasked values of an np.ma array (or of every value of an ndarray / tensor), any shape -- e.g. residuals pooled
-    over several image pairs as in test.py.  -> the reference's statistics dict (attribute access)."""
+    over several image pairs as in test.py.  -> the reference's statistics dict (attribute access); abs_quantiles / quantiles /
+    within as in evaluate_statistics."""
+    dist = _dist_options(abs_quantiles, quantiles, within)
     if torch.is_tensor(residuals_masked):
         dev = _device(residuals_masked.device if residuals_masked.is_cuda else device)
         r = residuals_masked.to(dev, torch.float64).reshape(-1).contiguous()
@@ -433,8 +560,12 @@ def get_statistics_masked(residuals_masked, residual_threshold=None, device="cud
         r = torch.zeros(1, dtype=torch.float64, device=dev)
         valid = torch.zeros(1, dtype=torch.uint8, device=dev)
     sets = [(0, 1, None)] + ([(0, 1, residual_threshold)] if residual_threshold else [])
-    res = _run_sets(r, None, valid, sets, dev)
-    return _stats_dict(res[0], res[1] if residual_threshold else None, residual_threshold)
+    if dist is None:
+        res = _run_sets(r, None, valid, sets, dev)
+        return _stats_dict(res[0], res[1] if residual_threshold else None, residual_threshold)
+    res, dres = _run_sets(r, None, valid, sets, dev, dist)
+    return _stats_dict(res[0], res[1] if residual_threshold else None, residual_threshold, dist, dres[0],
+                       dres[1] if residual_threshold else None)
 
 
 # ---- every pair plane of a sweep, and the pool of all pairs (test.py:191-357) ----------------------------------------------
@@ -453,6 +584,17 @@ def _queue_pooled(res, n_planes, p0, p1, cls, valid, sets, out, dev):
                                        ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats_pooled")
 
 
+def _queue_dist_pooled(res, n_planes, p0, p1, cls, valid, sets, dist, out, dev):
+    """rd_residual_dist_pooled over the sets of _queue_pooled into out [len(sets), dist.width] (device), enqueued only."""
+    n, ns = cls.numel(), len(sets)
+    lib = load()
+    need_a, thr_a = _set_arrays(sets)
+    ws = workspace(lib.rd_residual_dist_pooled_ws_bytes(n, ns, dist.n_q, dist.n_t), dev, slot=4)
+    check(lib.rd_residual_dist_pooled(ptr(res), n, n_planes, p0, p1, ptr(cls), ptr(valid), n, need_a, thr_a, ns, dist.q_a,
+                                      dist.mode_a, dist.n_q, dist.tau_a, dist.n_t, ptr(out), ws.data_ptr(), ws.numel(),
+                                      stream_ptr()), "residual_dist_pooled")
+
+
 def _is_sweep(x):
     return hasattr(x, "image_pairs") and hasattr(x, "pairs") and hasattr(x, "fused")
 
@@ -464,7 +606,7 @@ def _private_f64(x, dev):
 
 
 def _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
-                    fused, nodata, device):
+                    fused, nodata, device, dist=None):
     """-> (stats {'before', 'pairs', 'pooled'[, 'fused']}, classes)"""
     if _is_sweep(pairs):
         sweep, pairs = pairs, getattr(pairs, "device_pairs", None)
@@ -511,26 +653,44 @@ def _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_
                                           ptr(r_before), ptr(res), ptr(r_fused), ptr(cls), ptr(valid), stream_ptr()),
               "eval_classify_planes")
         psets = [(CLASS_BITS[c], t) for c in classes for t in ((None, thr) if thr else (None,))]
-        out = torch.empty((n_planes + 1, len(psets), 8), dtype=torch.float64, device=dev)
-        for p in range(n_planes):
-            _queue_pooled(res, n_planes, p, p + 1, cls, valid, psets, out[p], dev)
-        _queue_pooled(res, n_planes, 0, n_planes, cls, valid, psets, out[n_planes], dev)
+        # one device buffer for the eight numbers and, with options, the quantile rows behind them: one read-back
+        n_rows = (n_planes + 1) * len(psets)
+        buf = torch.empty(n_rows * (8 + (dist.width if dist else 0)), dtype=torch.float64, device=dev)
+        out = buf[:n_rows * 8].view(n_planes + 1, len(psets), 8)
+        dout = buf[n_rows * 8:].view(n_planes + 1, len(psets), dist.width) if dist else None
+        for p in range(n_planes + 1):                  # the pairs, then the pool of all of them
+            p0, p1 = (p, p + 1) if p < n_planes else (0, n_planes)
+            _queue_pooled(res, n_planes, p0, p1, cls, valid, psets, out[p], dev)
+            if dist is not None:
+                _queue_dist_pooled(res, n_planes, p0, p1, cls, valid, psets, dist, dout[p], dev)
     # the initial DSM and the fused surface: two sources of the existing sets kernel, off the same class byte
     sets = [(0, VALID_BEFORE | b, t) for b, t in psets]
     if fz is not None:
         sets += [(1, VALID_EXTRA | b, t) for b, t in psets]
-    single = _run_sets(r_before, r_fused, cls, sets, dev)
-    rows_out = out.cpu().numpy()
-    stats = AttrDict(before=_class_stats(single[:len(psets)], classes, thr),
-                     pairs=[_class_stats(rows_out[p], classes, thr) for p in range(n_planes)],
-                     pooled=_class_stats(rows_out[n_planes], classes, thr))
+    k = len(psets)
+    if dist is None:
+        single = _run_sets(r_before, r_fused, cls, sets, dev)
+        rows_out = out.cpu().numpy()
+        stats = AttrDict(before=_class_stats(single[:k], classes, thr),
+                         pairs=[_class_stats(rows_out[p], classes, thr) for p in range(n_planes)],
+                         pooled=_class_stats(rows_out[n_planes], classes, thr))
+        if fz is not None:
+            stats.fused = _class_stats(single[k:], classes, thr)
+        return stats, classes
+    single, dsingle = _run_sets(r_before, r_fused, cls, sets, dev, dist)
+    host = buf.cpu().numpy()
+    rows_out, drows = host[:n_rows * 8].reshape(out.shape), host[n_rows * 8:].reshape(dout.shape)
+    stats = AttrDict(before=_class_stats(single[:k], classes, thr, dist, dsingle[:k]),
+                     pairs=[_class_stats(rows_out[p], classes, thr, dist, drows[p]) for p in range(n_planes)],
+                     pooled=_class_stats(rows_out[n_planes], classes, thr, dist, drows[n_planes]))
     if fz is not None:
-        stats.fused = _class_stats(single[len(psets):], classes, thr)
+        stats.fused = _class_stats(single[k:], classes, thr, dist, dsingle[k:])
     return stats, classes
 
 
 def evaluate_pairs_statistics(pairs, initial, gt, area_defn=None, mask_gt=None, mask_building=None, mask_water=None,
-                              mask_forest=None, residual_threshold=None, *, fused=None, nodata=None, device="cuda"):
+                              mask_forest=None, residual_threshold=None, *, fused=None, nodata=None, device="cuda",
+                              abs_quantiles=None, quantiles=None, within=None):
     """The statistics of test.py:191-357 for the P predictions of a pair sweep, scored where the sweep left them: ONE
     dilation and ONE classification pass whatever P is (rd_eval_classify_planes), then every pair's statistics sets and the
     sets of the pool of all pairs' residuals (rd_residual_stats_pooled), and the initial DSM and the fused surface from the
@@ -540,26 +700,29 @@ def evaluate_pairs_statistics(pairs, initial, gt, area_defn=None, mask_gt=None, 
     are used when it carries them (keep_device=True), and its fused surface when `fused` is not given.  Device tensors are
     scored in place of residence and never written; host arrays are uploaded once.  Everything else as evaluate_statistics.
     -> {'before': {class: stats}, 'pairs': [P x {class: stats}], 'pooled': {class: stats}[, 'fused': {class: stats}]}, every
-    stats dict in the reference's get_statistics format (attribute access)."""
+    stats dict in the reference's get_statistics format (attribute access).  abs_quantiles / quantiles / within as in
+    evaluate_statistics: per pair and for the pool from rd_residual_dist_pooled (a quantile of the pool ranks the residuals of
+    all pairs together), for the initial DSM and the fused surface from rd_residual_dist_sets."""
     return _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest,
-                           residual_threshold, fused, nodata, device)[0]
+                           residual_threshold, fused, nodata, device, _dist_options(abs_quantiles, quantiles, within))[0]
 
 
 def evaluate_pairs_performance(pairs, ds_raster_input, ds_raster_gt, logger_root, area_defn=None, path_gt_mask=None,
                                path_building_mask=None, path_water_mask=None, path_forest_mask=None, loggers_stats=None,
                                logger_stats_pooled=None, residual_threshold=None, *, fused=None, nodata=None, gsd=None,
-                               device="cuda"):
+                               device="cuda", abs_quantiles=None, quantiles=None, within=None):
     """Drop-in for the evaluation of test.py:191-357: on loggers_stats[p] the report evaluate_performance writes for
     prediction p, and on logger_stats_pooled the "statistics over all predictions" block (test.py:326-357; written when
     there is more than one pair, as in the reference, or when the logger is given).  pairs / fused as
     evaluate_pairs_statistics, every other argument as evaluate_performance.  -> the statistics object of
-    evaluate_pairs_statistics; the residual rasters are not returned (evaluate_performance per plane gives them)."""
+    evaluate_pairs_statistics; the residual rasters are not returned (evaluate_performance per plane gives them).
+    abs_quantiles / quantiles / within (see evaluate_statistics) add their lines to every block of every report."""
     gt, init, nodata, gsd, mask_gt, mask_b, mask_w, mask_f = _performance_inputs(
         ds_raster_input, ds_raster_gt, logger_root, path_gt_mask, path_building_mask, path_water_mask, path_forest_mask,
         nodata, gsd, "evaluate_pairs_performance")
     logger_root.info("\tCompute residual errors and statistics before and after the refinement...")
     stats, classes = _evaluate_pairs(pairs, init, gt, area_defn, mask_gt, mask_b, mask_w, mask_f, residual_threshold,
-                                     fused, nodata, device)
+                                     fused, nodata, device, _dist_options(abs_quantiles, quantiles, within))
     n_planes = len(stats.pairs)
     if loggers_stats is None:
         loggers_stats = [_default_stats_logger()] * n_planes

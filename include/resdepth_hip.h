@@ -56,7 +56,7 @@ typedef void* rd_stream_t; /* hipStream_t */
 #define RD_ERR_WS 2
 #define RD_ERR_HIP 3
 
-int rd_version(void); /* 100: r01-r03; 101: rd_set_splitk_workspace registrations belong to (current device, stream); 102: rd_host_register & co; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next / rd_amax, packed operands hold both split forms; 106: rd_plan_*; 107: rd_quant_next_img; 109: rd_assemble_grid_tiles; 110: rd_patch_moments, rd_region_moments, rd_assemble_train_patches; 111: test-time augmentation, resdepth_hip_tta.h (rd_assemble_grid_tiles_aug, rd_blend_accumulate_tta); 112: one-pass sweep of all image pairs, resdepth_hip_pairs.h (rd_blend_accumulate_planes, rd_fuse_planes); 113: scoring the planes of a pair sweep, resdepth_hip_eval.h (rd_eval_classify_planes, rd_residual_stats_pooled); 114: resdepth_hip_loss.h; 115: resdepth_hip_optim.h; 116: quantiles and within-tolerance shares of the statistics sets, resdepth_hip_dist.h */
+int rd_version(void); /* 100: r01-r03; 101: rd_set_splitk_workspace registrations belong to (current device, stream); 102: rd_host_register & co; 103: rd_mfma_products; 104: rd_adam_step_dev; 105 (r06): rd_quant_next / rd_amax, packed operands hold both split forms; 106: rd_plan_*; 107: rd_quant_next_img; 109: rd_assemble_grid_tiles; 110: rd_patch_moments, rd_region_moments, rd_assemble_train_patches; 111: test-time augmentation, resdepth_hip_tta.h (rd_assemble_grid_tiles_aug, rd_blend_accumulate_tta); 112: one-pass sweep of all image pairs, resdepth_hip_pairs.h (rd_blend_accumulate_planes, rd_fuse_planes); 113: scoring the planes of a pair sweep, resdepth_hip_eval.h (rd_eval_classify_planes, rd_residual_stats_pooled); 114: resdepth_hip_loss.h; 115: resdepth_hip_optim.h; 116: quantiles and within-tolerance shares of the statistics sets, resdepth_hip_dist.h; still 116 (tests/test_dist_cpu.py pins the number): cell grids, slope and covariate bins, resdepth_hip_errmap.h -- look for the symbols, not the number */
 /* Arithmetic of the split MFMA kernels -- ONE library, chosen per launch (csrc/rd_mfma_dev.h):
  *   6  "split3"   x = x1 + x2 + x3 (three bf16 terms, exact), six products per multiply on v_mfma_f32_32x32x16_bf16.  No
  *                 assumption about the operands; what every launch falls back to.
@@ -649,4 +649,5 @@ int rd_prof_collect(rd_prof_entry* out, int max_entries); /* returns number of c
 #include "resdepth_hip_loss.h" /* masked L2 / Huber / slope-consistency training losses and the MAE beside them */
 #include "resdepth_hip_optim.h" /* global norm and non-finite count of the flat gradient */
 #include "resdepth_hip_dist.h" /* error quantiles (LE90) and within-tolerance shares of the statistics sets */
+#include "resdepth_hip_errmap.h" /* statistics per cell of a grid, Horn's slope, covariate bins as class bytes */
 #endif /* RESDEPTH_HIP_H */

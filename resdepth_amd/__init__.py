@@ -14,8 +14,9 @@ from .inference import predict_linear_blend, SyntheticRasterTiles  # noqa: F401
 from .ensemble import PairSweep, predict_pairs_linear_blend  # noqa: F401
 from .sampler import GpuGridTiles, GpuPatchSampler, GpuTrainSet, GpuValSet, SamplerLoader  # noqa: F401
 from . import normalization  # noqa: F401
-from .evaluation import (dilate_mask, evaluate_pairs_performance, evaluate_pairs_statistics,  # noqa: F401
-                         evaluate_performance, evaluate_statistics, get_statistics_masked, print_statistics)
+from .evaluation import (dilate_mask, dsm_slope, error_map, evaluate_binned, evaluate_pairs_performance,  # noqa: F401
+                         evaluate_pairs_statistics, evaluate_performance, evaluate_statistics, get_statistics_masked,
+                         print_binned, print_statistics)
 from .factories import (get_loss, get_model, get_scheduler, get_trainer, valid_tile_size,  # noqa: F401
                         validate_tile_size)
 
@@ -23,4 +24,4 @@ __all__ = ["UNet", "SkipConnection", "MaskedL1Loss", "masked_l1_loss", "MaskedLo
            "SyntheticDsmOrthoDataset", "synthetic_batch", "predict_linear_blend", "SyntheticRasterTiles", "predict_pairs_linear_blend", "PairSweep",
            "GpuPatchSampler", "SamplerLoader", "GpuGridTiles", "GpuTrainSet", "GpuValSet", "normalization", "get_loss", "get_model", "get_scheduler", "get_trainer", "valid_tile_size", "validate_tile_size",
            "dilate_mask", "evaluate_statistics", "evaluate_performance", "print_statistics", "get_statistics_masked",
-           "evaluate_pairs_statistics", "evaluate_pairs_performance"]
+           "evaluate_pairs_statistics", "evaluate_pairs_performance", "dsm_slope", "error_map", "evaluate_binned", "print_binned"]

@@ -199,6 +199,14 @@ SIGNATURES_DIST = {
 }
 # the constants of that header
 DIST_MAX_Q, DIST_MAX_T = 8, 8
+# include/resdepth_hip_errmap.h (statistics per cell of a grid, Horn's slope, covariate bins as class bytes), one to one as above
+SIGNATURES_ERRMAP = {
+    "rd_cell_stats": (I, [P, P, I, I, I, I, I, D, P, P]),
+    "rd_dsm_slope": (I, [P, I, I, I, D, D, D, P, P]),
+    "rd_bin_classes": (I, [P, I, P, LL, P, I, P, P]),
+}
+# the constants of that header
+CELL_MIN, CELL_MAX, BIN_MAX = 4, 256, 24
 
 
 class ProfEntry(C.Structure):
@@ -221,7 +229,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
                 + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()) \
-                + list(SIGNATURES_DIST.items()):
+                + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

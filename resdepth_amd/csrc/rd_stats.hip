@@ -412,6 +412,26 @@ struct SetMoments {
         }
     }
 
+    // store()'s tree for ONE set, left in LDS: o[0..4] = the block's count, sum|r|, sum r^2, min, max of set s, written by
+    // thread 0 and visible to the block on return; every thread of the block is here (cell_stats_kernel)
+    __device__ __forceinline__ void reduce(int s, double (*red)[5], double* o) const {
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const double v0 = wave_sum(cnt[s]), v1 = wave_sum(sa[s]), v2 = wave_sum(sq[s]), v3 = wave_min(mn[s]),
+                     v4 = wave_max(mx[s]);
+        if (lane == 0) {
+            red[w][0] = v0; red[w][1] = v1; red[w][2] = v2; red[w][3] = v3; red[w][4] = v4;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+            o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+            o[2] = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+            o[3] = fmin(fmin(red[0][3], red[1][3]), fmin(red[2][3], red[3][3]));
+            o[4] = fmax(fmax(red[0][4], red[1][4]), fmax(red[2][4], red[3][4]));
+        }
+        __syncthreads();
+    }
+
     // partial[(block * n_sets + s) * 5 + q]: the block's moments of set s, waves added in a fixed order
     __device__ __forceinline__ void store(double* __restrict__ partial, const SetSpecs& sp, double (*red)[5]) const {
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1422,6 +1442,295 @@ int rd_fuse_planes(const double* planes, long long plane_stride, int n_planes, l
 #undef RD_FUSE_CASE
     }
     RD_LAUNCH_CHECK("fuse_planes");
+    return RD_OK;
+}
+
+}  // extern "C"
+
+// ---- where the error is and on what ground (include/resdepth_hip_errmap.h) -------------------------------------------------
+// cell_stats_kernel: the statistics engine turned inside out -- not few sets of many values with global histograms and a launch
+// per pass, but one block per cell with everything in the block.  The moments are SetMoments with one set (a thread adds its
+// pixels in row-major order, the block adds its threads in SetMoments::reduce's tree); the medians are the engine's radix
+// select on the same keys with the same two ranks per selector, the pass histograms in LDS, the pick a block-wide scan like
+// sets_pick_kernel's.  Phase 0 selects the median and the absolute median out of the same eight reads of the cell, phase 1 the
+// NMAD around the absolute median.  Each pass reads the cell's pixels again, consecutive lanes along x; LDS holds the
+// histograms only, so a 4 x 4 and a 256 x 256 cell take the same path.
+// dsm_slope_kernel: Horn's slope from a tile staged in LDS with its halo, like dilate_kernel; every operation through the
+// round-to-nearest intrinsics so that nothing is contracted.
+// bin_classes_kernel: the bin of a covariate value by counting the edges at or below it (the edges travel by value).
+namespace rd {
+
+constexpr int SLOPE_TW = 64, SLOPE_TH = 16;
+static_assert(RD_SLOPE_MAX_ROWS == 65535 * SLOPE_TH, "grid.y of dsm_slope_kernel");
+
+struct BinEdges {
+    int n_bins;
+    double e[RD_BIN_MAX + 1];
+};
+
+// a thread's walk over the w x h pixels of a cell: pixel t, t + 256, ... in row-major order, without a division per pixel
+struct CellWalk {
+    int x, y, dx, dy, w;
+    __device__ __forceinline__ CellWalk(int w_) : x(threadIdx.x % w_), y(threadIdx.x / w_), dx(256 % w_), dy(256 / w_), w(w_) {}
+    __device__ __forceinline__ void next() {
+        x += dx;
+        y += dy;
+        if (x >= w) {
+            x -= w;
+            ++y;
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void cell_stats_kernel(const double* __restrict__ src, const uint8_t* __restrict__ cls,
+                                                         int rows, int cols, int cell_h, int cell_w, int ncx, unsigned need,
+                                                         double thr, double* __restrict__ out) {
+    __shared__ double red[4][5];
+    __shared__ double mom[5];
+    __shared__ unsigned lh[2][2][256];                 // [selector][side][bin]
+    __shared__ unsigned wtot[4][4];                    // [histogram][wave]: the waves' totals of the pick's scan
+    __shared__ unsigned long long pf[2][2];            // [selector][rank]: the key prefix found so far
+    __shared__ unsigned rk[2][2];                      // the rank among the values under that prefix
+    __shared__ int bin_of[2][2];
+    __shared__ unsigned below_of[2][2];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int cy = blockIdx.x / ncx, cx = blockIdx.x - cy * ncx;
+    const int y0 = cy * cell_h, x0 = cx * cell_w;
+    const int h = min(cell_h, rows - y0), w = min(cell_w, cols - x0);
+    const double* __restrict__ sp0 = src + (long)y0 * cols + x0;
+    const uint8_t* __restrict__ cp0 = cls + (long)y0 * cols + x0;
+    double* __restrict__ o = out + (long)blockIdx.x * 8;
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+
+    SetSpecs sp;
+    sp.n = 1;
+    for (int i = 0; i < RD_STATS_MAX_SETS; ++i) {
+        sp.src[i] = 0;
+        sp.need[i] = need;
+        sp.thr[i] = thr;
+    }
+    {
+        SetMoments m;
+        for (CellWalk p(w); p.y < h; p.next()) {
+            const long i = (long)p.y * cols + p.x;
+            const double d = sp0[i];
+            m.add(sp, cp0[i], [&](int) { return d; });
+        }
+        m.reduce(0, red, mom);
+    }
+    const double cnt = mom[0];
+    if (t == 0) {
+        o[0] = cnt;
+        o[1] = cnt > 0 ? mom[4] : nanv;
+        o[2] = cnt > 0 ? mom[3] : nanv;
+        o[3] = cnt > 0 ? mom[1] / cnt : nanv;
+        o[4] = cnt > 0 ? sqrt(mom[2] / cnt) : nanv;
+    }
+    if (!(cnt > 0)) {                                  // block-uniform
+        if (t == 0) o[5] = o[6] = o[7] = nanv;
+        return;
+    }
+    const unsigned c = (unsigned)cnt;
+    double shift = 0.0;
+    for (int phase = 0; phase < 2; ++phase) {
+        // selector j of phase 0: 0 the absolute median (value mode 1), 1 the median (mode 0); of phase 1: the NMAD (mode 2)
+        const int nsel = phase == 0 ? 2 : 1;
+        if (t < 4) {
+            pf[t >> 1][t & 1] = 0ull;
+            rk[t >> 1][t & 1] = (t & 1) ? c / 2 : (c - 1) / 2;
+        }
+        for (int pass = 7; pass >= 0; --pass) {
+            for (int i = t; i < 2 * 2 * 256; i += 256) (&lh[0][0][0])[i] = 0u;
+            __syncthreads();
+            const unsigned long long p00 = pf[0][0], p01 = pf[0][1], p10 = pf[1][0], p11 = pf[1][1];
+            const int hs = 8 * (pass + 1);
+            for (CellWalk p(w); p.y < h; p.next()) {
+                const long i = (long)p.y * cols + p.x;
+                const double r = sp0[i];
+                if (!in_set(sp, 0, cp0[i], r)) continue;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    if (j >= nsel) continue;
+                    const unsigned long long k = key_of(pick_value(r, phase == 0 ? 1 - j : 2, shift));
+                    const unsigned long long hi = pass == 7 ? 0ull : (k >> hs);
+                    const unsigned b = (unsigned)((k >> (8 * pass)) & 255ull);
+                    if (hi == (j ? p10 : p00))
+                        atomicAdd(&lh[j][0][b], 1u);
+                    else if (hi == (j ? p11 : p01))
+                        atomicAdd(&lh[j][1][b], 1u);
+                }
+            }
+            __syncthreads();
+            // the pick: thread t holds bin t of the four histograms (selector j, rank q); while a selector's two prefixes agree
+            // both of its ranks read side 0.  An inclusive scan per histogram: shuffles inside a wave, the waves' totals in LDS
+            unsigned cb[4], incl[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = q >> 1, side = q & 1;
+                const bool same = (j ? p10 == p11 : p00 == p01);
+                cb[q] = j < nsel ? lh[j][side && !same ? 1 : 0][t] : 0u;
+                unsigned v = cb[q];
+                for (int off = 1; off < 64; off <<= 1) {
+                    const unsigned u = __shfl_up(v, off);
+                    if (lane >= off) v += u;
+                }
+                incl[q] = v;
+                if (lane == 63) wtot[q][wv] = v;
+            }
+            if (t < 4) {
+                bin_of[t >> 1][t & 1] = 255;
+                below_of[t >> 1][t & 1] = 0u;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = q >> 1, side = q & 1;
+                unsigned base = 0u;
+                for (int u = 0; u < 4; ++u)
+                    if (u < wv) base += wtot[q][u];
+                const unsigned in = incl[q] + base, ex = in - cb[q];
+                const unsigned rank = rk[j][side];
+                if (cb[q] && ex <= rank && rank < in) {
+                    bin_of[j][side] = t;
+                    below_of[j][side] = ex;
+                }
+            }
+            __syncthreads();
+            if (t < 4) {
+                const int j = t >> 1, side = t & 1;
+                pf[j][side] = (pf[j][side] << 8) | (unsigned long long)bin_of[j][side];
+                rk[j][side] -= below_of[j][side];
+            }
+            __syncthreads();
+        }
+        if (phase == 0) {
+            const double am = 0.5 * (unkey(pf[0][0]) + unkey(pf[0][1]));
+            if (t == 0) {
+                o[5] = am;
+                o[6] = 0.5 * (unkey(pf[1][0]) + unkey(pf[1][1]));
+            }
+            shift = am;
+            __syncthreads();                            // every thread has read the prefixes before they are cleared
+        } else if (t == 0) {
+            o[7] = 1.4826 * (0.5 * (unkey(pf[0][0]) + unkey(pf[0][1])));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void dsm_slope_kernel(const void* __restrict__ dsm, int f64, int rows, int cols,
+                                                        double nodata, double run_x, double run_y,
+                                                        double* __restrict__ slope) {
+    constexpr int PW = SLOPE_TW + 2, PH = SLOPE_TH + 2;
+    __shared__ double tile[PH * PW];                   // NaN: nodata, NaN or outside the raster
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    const int ox = blockIdx.x * SLOPE_TW, oy = blockIdx.y * SLOPE_TH;
+    for (int i = threadIdx.x; i < PH * PW; i += blockDim.x) {
+        const int ty = i / PW, tx = i - ty * PW;
+        const int y = oy - 1 + ty, x = ox - 1 + tx;
+        double v = nanv;
+        if (y >= 0 && y < rows && x >= 0 && x < cols) {
+            v = load_f(dsm, f64, (long)y * cols + x);
+            if (v == nodata) v = nanv;
+        }
+        tile[i] = v;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < SLOPE_TH * SLOPE_TW; i += blockDim.x) {
+        const int ty = i / SLOPE_TW, tx = i - ty * SLOPE_TW;
+        const int y = oy + ty, x = ox + tx;
+        if (y >= rows || x >= cols) continue;
+        const double* r0 = tile + ty * PW + tx;        // the row above, starting at the left neighbour
+        const double a = r0[0], b = r0[1], c = r0[2];
+        const double d = r0[PW], e = r0[PW + 1], f = r0[PW + 2];
+        const double g = r0[2 * PW], hh = r0[2 * PW + 1], ii = r0[2 * PW + 2];
+        const bool bad = isnan(a) || isnan(b) || isnan(c) || isnan(d) || isnan(e) || isnan(f) || isnan(g) || isnan(hh) ||
+                         isnan(ii);
+        const double east = __dadd_rn(__dadd_rn(c, __dmul_rn(2.0, f)), ii);
+        const double west = __dadd_rn(__dadd_rn(a, __dmul_rn(2.0, d)), g);
+        const double south = __dadd_rn(__dadd_rn(g, __dmul_rn(2.0, hh)), ii);
+        const double north = __dadd_rn(__dadd_rn(a, __dmul_rn(2.0, b)), c);
+        const double p = __ddiv_rn(__dsub_rn(east, west), run_x);
+        const double q = __ddiv_rn(__dsub_rn(south, north), run_y);
+        const double v = __dsqrt_rn(__dadd_rn(__dmul_rn(p, p), __dmul_rn(q, q)));
+        slope[(long)y * cols + x] = bad ? nanv : v;
+    }
+}
+
+__global__ __launch_bounds__(256) void bin_classes_kernel(const void* __restrict__ by, int f64, const uint8_t* __restrict__ cls,
+                                                          long n, BinEdges ed, int groups, uint8_t* __restrict__ out) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const double v = load_f(by, f64, i);
+        int at_or_below = 0;                           // edges <= v: 0 for a NaN
+#pragma unroll
+        for (int k = 0; k <= RD_BIN_MAX; ++k) at_or_below += (k <= ed.n_bins && v >= ed.e[k]) ? 1 : 0;
+        const int b = at_or_below - 1;                 // -1: below the first edge; n_bins: at or above the last one
+        const unsigned valid = cls[i] & 3u;
+        const bool binned = b >= 0 && b < ed.n_bins;
+        for (int g = 0; g < groups; ++g) {
+            const int q = b - 6 * g;
+            out[(long)g * n + i] = (uint8_t)(valid | ((binned && q >= 0 && q < 6) ? (4u << q) : 0u));
+        }
+    }
+}
+
+}  // namespace rd
+
+extern "C" {
+
+int rd_cell_stats(const double* src, const uint8_t* cls, int rows, int cols, int cell_h, int cell_w, int need, double thr,
+                  double* out, rd_stream_t s_) {
+    RD_REQUIRE(src && cls && out, "rd_cell_stats: null pointer");
+    RD_REQUIRE(rows >= 1 && cols >= 1, "rd_cell_stats: bad shape (rows=%d cols=%d)", rows, cols);
+    RD_REQUIRE(cell_h >= RD_CELL_MIN && cell_h <= RD_CELL_MAX && cell_w >= RD_CELL_MIN && cell_w <= RD_CELL_MAX,
+               "rd_cell_stats: cell %d x %d, sides must be in %d..%d", cell_h, cell_w, RD_CELL_MIN, RD_CELL_MAX);
+    RD_REQUIRE(need >= 0 && need <= 255, "rd_cell_stats: need %d outside 0..255", need);
+    RD_REQUIRE(thr >= 0.0 && thr <= 1.7976931348623157e308, "rd_cell_stats: threshold %g must be finite and >= 0", thr);
+    const long ncy = (rows + cell_h - 1) / cell_h, ncx = (cols + cell_w - 1) / cell_w;
+    // one block of 256 threads per cell, and a launch holds fewer than 2^32 threads
+    RD_REQUIRE(ncy * ncx < (long)RD_CELL_MAX_CELLS, "rd_cell_stats: %ld x %ld cells, a call takes fewer than %d", ncy, ncx,
+               RD_CELL_MAX_CELLS);
+    hipStream_t s = (hipStream_t)s_;
+    // algorithmic bytes: 17 reads of every pixel's value and class byte, one row of eight doubles per cell
+    ProfScope ps(s, "cell_stats", 0, 17.0 * 9.0 * rows * cols + 64.0 * ncy * ncx);
+    RD_LAUNCH(cell_stats_kernel, dim3((unsigned)(ncy * ncx)), dim3(256), 0, s, src, cls, rows, cols, cell_h, cell_w, (int)ncx,
+              (unsigned)need, thr, out);
+    RD_LAUNCH_CHECK("cell_stats");
+    return RD_OK;
+}
+
+int rd_dsm_slope(const void* dsm, int dsm_f64, int rows, int cols, double nodata, double gsd_x, double gsd_y, double* slope,
+                 rd_stream_t s_) {
+    RD_REQUIRE(dsm && slope && (const void*)slope != dsm, "rd_dsm_slope: null or aliased pointer");
+    RD_REQUIRE(rows >= 1 && cols >= 1, "rd_dsm_slope: bad shape (rows=%d cols=%d)", rows, cols);
+    RD_REQUIRE(gsd_x > 0.0 && gsd_x <= 1.7976931348623157e308 && gsd_y > 0.0 && gsd_y <= 1.7976931348623157e308,
+               "rd_dsm_slope: GSD %g x %g must be positive and finite", gsd_x, gsd_y);
+    RD_REQUIRE(rows <= RD_SLOPE_MAX_ROWS, "rd_dsm_slope: %d rows (at most %d: 65535 tiles of %d rows)", rows, RD_SLOPE_MAX_ROWS,
+               SLOPE_TH);
+    hipStream_t s = (hipStream_t)s_;
+    ProfScope ps(s, "dsm_slope", 0, (double)rows * cols * ((dsm_f64 ? 8.0 : 4.0) + 8.0));
+    const dim3 grid((cols + SLOPE_TW - 1) / SLOPE_TW, (rows + SLOPE_TH - 1) / SLOPE_TH);
+    RD_LAUNCH(dsm_slope_kernel, grid, dim3(256), 0, s, dsm, dsm_f64 ? 1 : 0, rows, cols, nodata, 8.0 * gsd_x, 8.0 * gsd_y, slope);
+    RD_LAUNCH_CHECK("dsm_slope");
+    return RD_OK;
+}
+
+int rd_bin_classes(const void* by, int by_f64, const uint8_t* cls, long long n, const double* edges, int n_bins, uint8_t* out,
+                   rd_stream_t s_) {
+    RD_REQUIRE(by && cls && edges && out, "rd_bin_classes: null pointer");
+    RD_REQUIRE(n >= 1, "rd_bin_classes: n = %lld", n);
+    RD_REQUIRE(n_bins >= 1 && n_bins <= RD_BIN_MAX, "rd_bin_classes: %d bins (1..%d)", n_bins, RD_BIN_MAX);
+    BinEdges ed;
+    ed.n_bins = n_bins;
+    for (int k = 0; k <= RD_BIN_MAX; ++k) ed.e[k] = k <= n_bins ? edges[k] : 0.0;
+    for (int k = 0; k <= n_bins; ++k) RD_REQUIRE(ed.e[k] == ed.e[k], "rd_bin_classes: edge %d is NaN", k);
+    for (int k = 0; k < n_bins; ++k)
+        RD_REQUIRE(ed.e[k] < ed.e[k + 1], "rd_bin_classes: edges %d and %d do not increase (%g, %g)", k, k + 1, ed.e[k],
+                   ed.e[k + 1]);
+    const int groups = (n_bins + 5) / 6;
+    hipStream_t s = (hipStream_t)s_;
+    ProfScope ps(s, "bin_classes", 0, (double)n * ((by_f64 ? 8.0 : 4.0) + 1.0 + groups));
+    RD_LAUNCH(bin_classes_kernel, dim3(stats_grid((long)n)), dim3(256), 0, s, by, by_f64 ? 1 : 0, cls, (long)n, ed, groups, out);
+    RD_LAUNCH_CHECK("bin_classes");
     return RD_OK;
 }
 

@@ -299,13 +299,14 @@ def _eval_inputs(rows, cols, area_defn, mask_gt, mask_building, mask_water, mask
     return gm, bdil, bnod, water, forest, classes, rect_a, (-1 if rects is None else len(rects)), nd
 
 
-def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
-              nodata, dev, dist=None):
-    """-> (stats {'before', 'after'}, r_after, cls, classes) with r_after / cls on the device."""
+def _classified(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev, who):
+    """The classification pass (rd_eval_classify) -> (r_before, r_after, cls, classes), all on the device.  initial None: the
+    prediction stands in for it (r_before is then r_after and RD_CLS_VALID_BEFORE equals RD_CLS_VALID_AFTER)."""
     pred = _on(prediction, dev, torch.float64)
-    init, g = _float_raster(initial, dev), _float_raster(gt, dev)
-    if pred.dim() != 2 or pred.shape != init.shape or pred.shape != g.shape:
-        raise ValueError(f"evaluate: prediction {tuple(pred.shape)}, initial {tuple(init.shape)} and ground truth "
+    init = pred if initial is None else _float_raster(initial, dev)
+    g = _float_raster(gt, dev)
+    if pred.dim() != 2 or pred.numel() == 0 or pred.shape != init.shape or pred.shape != g.shape:
+        raise ValueError(f"{who}: prediction {tuple(pred.shape)}, initial {tuple(init.shape)} and ground truth "
                          f"{tuple(g.shape)} must be equal 2-D rasters")
     rows, cols = pred.shape
     gm, bdil, bnod, water, forest, classes, rect_a, n_rects, nd = _eval_inputs(
@@ -313,12 +314,19 @@ def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_w
     r_before = torch.empty((rows, cols), dtype=torch.float64, device=dev)
     r_after = torch.empty_like(r_before)
     cls = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-    lib = load()
     with torch.cuda.device(dev):
-        check(lib.rd_eval_classify(ptr(pred), ptr(init), int(init.dtype == torch.float64), ptr(g),
-                                   int(g.dtype == torch.float64), ptr(gm), ptr(bdil), ptr(bnod), ptr(water), ptr(forest),
-                                   rect_a, n_rects, rows, cols, nd, ptr(r_before), ptr(r_after), ptr(cls), stream_ptr()),
+        check(load().rd_eval_classify(ptr(pred), ptr(init), int(init.dtype == torch.float64), ptr(g),
+                                      int(g.dtype == torch.float64), ptr(gm), ptr(bdil), ptr(bnod), ptr(water), ptr(forest),
+                                      rect_a, n_rects, rows, cols, nd, ptr(r_before), ptr(r_after), ptr(cls), stream_ptr()),
               "eval_classify")
+    return r_before, r_after, cls, classes
+
+
+def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, residual_threshold,
+              nodata, dev, dist=None):
+    """-> (stats {'before', 'after'}, r_after, cls, classes) with r_after / cls on the device."""
+    r_before, r_after, cls, classes = _classified(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water,
+                                                  mask_forest, nodata, dev, "evaluate")
     thr = residual_threshold
     sets = [(src, valid | CLASS_BITS[c], t) for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)) for c in classes
             for t in ((None, thr) if thr else (None,))]
@@ -743,3 +751,187 @@ def evaluate_pairs_performance(pairs, ds_raster_input, ds_raster_gt, logger_root
             logger_stats_pooled.info("\n{}\n{}\n".format(title, "-" * len(title)))
             print_statistics(stats.pooled[c], logger_stats_pooled)
     return stats
+
+
+# ---- where the error is and on what ground: cell grids, slope, covariate bins (include/resdepth_hip_errmap.h) -----------------
+CELL_MIN, CELL_MAX, BIN_MAX = 4, 256, 24              # RD_CELL_MIN, RD_CELL_MAX, RD_BIN_MAX
+MAX_CELLS = 1 << 24                                   # RD_CELL_MAX_CELLS
+BINS_PER_PLANE = 6                                    # bin bits of one class-byte plane of rd_bin_classes (bits 2..7)
+
+
+def _pair_of(v, what, cast):
+    """scalar or (first, second) -> (first, second)"""
+    if isinstance(v, (tuple, list)) or (hasattr(v, "shape") and len(getattr(v, "shape")) == 1):
+        if len(v) != 2:
+            raise ValueError(f"{what}: expected a scalar or a pair, got {v!r}")
+        return cast(v[0]), cast(v[1])
+    return cast(v), cast(v)
+
+
+def _slope_tangent(d, gsd, nodata, who):
+    """device f32 / f64 raster -> device fp64 raster of rd_dsm_slope (rise over run); the arguments checked on the host"""
+    if gsd is None:
+        raise ValueError(f"{who}: the slope needs gsd= (a scalar or (gsd_y, gsd_x))")
+    gsd_y, gsd_x = _pair_of(gsd, f"{who}: gsd", float)
+    if not (0.0 < gsd_x < float("inf") and 0.0 < gsd_y < float("inf")):
+        raise ValueError(f"{who}: gsd {gsd!r} must be positive and finite")
+    if d.dim() != 2 or d.numel() == 0:
+        raise ValueError(f"{who}: expected a non-empty 2-D raster, got shape {tuple(d.shape)}")
+    rows, cols = d.shape
+    out = torch.empty((rows, cols), dtype=torch.float64, device=d.device)
+    nd = float("nan") if nodata is None else float(nodata)
+    with torch.cuda.device(d.device):
+        check(load().rd_dsm_slope(ptr(d), int(d.dtype == torch.float64), rows, cols, nd, gsd_x, gsd_y, ptr(out), stream_ptr()),
+              "dsm_slope")
+    return out
+
+
+def dsm_slope(dsm, gsd, nodata=-9999, degrees=True, device="cuda"):
+    """Horn's 3 x 3 slope of a DSM (rd_dsm_slope, include/resdepth_hip_errmap.h) -> device fp64 raster: the slope angle in
+    degrees, or with degrees=False its tangent (rise over run) exactly as the kernel leaves it.  dsm: 2-D array / tensor, f32 and
+    f64 read as given; gsd: a scalar or (gsd_y, gsd_x).  NaN where any pixel of the 3 x 3 neighbourhood is nodata, NaN or outside
+    the raster (so on the border ring)."""
+    dev = _first_device(dsm, default=device)
+    slope = _slope_tangent(_float_raster(dsm, dev), gsd, nodata, "dsm_slope")
+    return torch.rad2deg(torch.atan(slope)) if degrees else slope
+
+
+def _threshold(thr, who):
+    """residual_threshold -> the thr of the C ABI (0: none)"""
+    if not thr:
+        return 0.0
+    thr = float(thr)
+    if not 0.0 < thr < float("inf"):
+        raise ValueError(f"{who}: residual_threshold {thr} must be positive and finite")
+    return thr
+
+
+def error_map(prediction, gt, cell, *, initial=None, area_defn=None, mask_gt=None, mask_building=None, mask_water=None,
+              mask_forest=None, nodata=-9999, residual_threshold=None, klass=None, device="cuda"):
+    """The accuracy map of a refined DSM: the eight statistics of evaluate_statistics for every cell of a grid of cell x cell
+    pixels (cell: an int or (cell_h, cell_w), 4..256; the ragged border cells included), by one rd_cell_stats launch on the
+    residuals and class bytes of the classification pass evaluate_statistics runs (same masks, same area, same nodata rule).
+
+    klass: one of the report's classes ("building", "terrain", "terrain_nowater", "terrain_nowater_noforest"; the masks that
+    define it must be given), None or "all": every valid pixel.  residual_threshold: only |residual| <= threshold counts.
+    -> AttrDict: refined [ncy, ncx, 8] (device fp64; an empty cell holds count 0 and NaN), initial (the same for the initial DSM,
+    when given), keys (the eight names in order), cell (cell_h, cell_w) and origin (0, 0): cell (cy, cx) covers rows
+    cy * cell_h .. and columns cx * cell_w .. of the raster."""
+    cell_h, cell_w = _pair_of(cell, "error_map: cell", int)
+    if not (CELL_MIN <= cell_h <= CELL_MAX and CELL_MIN <= cell_w <= CELL_MAX):
+        raise ValueError(f"error_map: cell {cell_h} x {cell_w}, sides must be in {CELL_MIN}..{CELL_MAX}")
+    thr = _threshold(residual_threshold, "error_map")
+    dev = _first_device(prediction, initial, gt, default=device)
+    r_before, r_after, cls, classes = _classified(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water,
+                                                  mask_forest, nodata, dev, "error_map")
+    klass = "all" if klass is None else klass
+    if klass not in classes:
+        raise ValueError(f"error_map: class {klass!r} is not defined by the masks given (have {classes})")
+    rows, cols = cls.shape
+    ncy, ncx = -(-rows // cell_h), -(-cols // cell_w)
+    if ncy * ncx >= MAX_CELLS:
+        raise ValueError(f"error_map: {ncy} x {ncx} cells, a call takes fewer than {MAX_CELLS}")
+    res = AttrDict(keys=list(_KEYS), cell=(cell_h, cell_w), origin=(0, 0))
+    lib = load()
+    with torch.cuda.device(dev):
+        for name, r, valid in (("refined", r_after, VALID_AFTER),) + ((("initial", r_before, VALID_BEFORE),)
+                                                                      if initial is not None else ()):
+            out = torch.empty((ncy, ncx, 8), dtype=torch.float64, device=dev)
+            check(lib.rd_cell_stats(ptr(r), ptr(cls), rows, cols, cell_h, cell_w, valid | CLASS_BITS[klass], thr, ptr(out),
+                                    stream_ptr()), "cell_stats")
+            res[name] = out
+    return res
+
+
+def _bin_edges(edges, who):
+    e = [float(v) for v in edges]
+    if not 1 <= len(e) - 1 <= BIN_MAX:
+        raise ValueError(f"{who}: {len(e)} edges, expected 2..{BIN_MAX + 1} ({BIN_MAX} bins at most)")
+    if any(v != v for v in e) or any(not a < b for a, b in zip(e, e[1:])):
+        raise ValueError(f"{who}: edges must increase strictly and hold no NaN (got {e})")
+    return e
+
+
+def _degrees_to_tangent(e):
+    """an edge in degrees -> the tangent the slope raster stores, in fp64 on the host (the infinities stay)"""
+    import math
+    return e if math.isinf(e) else math.tan(math.radians(e))
+
+
+def evaluate_binned(prediction, initial, gt, by, edges, *, gsd=None, area_defn=None, mask_gt=None, nodata=-9999,
+                    residual_threshold=None, device="cuda"):
+    """The statistics of evaluate_statistics (class "all") as a function of a covariate: one statistics dict for the initial and
+    one for the refined DSM per bin [edges[b], edges[b + 1]) of `by` (at most 24 bins, -inf / +inf allowed at the ends; a pixel
+    whose covariate is NaN or outside the edges is in no bin).
+
+    by: a raster of the DSMs' shape (array / tensor, f32 / f64 read as given), or "slope": Horn's slope of `gt` (rd_dsm_slope;
+    needs gsd= as a scalar or (gsd_y, gsd_x)) with the edges in DEGREES -- they are converted on the host, tan(radians(e)) in
+    fp64, and the pixels are binned on the stored tangent raster, so by="slope" and by=dsm_slope(gt, gsd, nodata,
+    degrees=False) with those converted edges give the same bits.
+    rd_bin_classes writes the bins as class bytes, six bins to a plane, in one pass; every bin is then an ordinary set (validity
+    bit | bin bit) of rd_residual_stats_sets, up to 20 sets per call, all enqueued before the one read-back.
+    -> [AttrDict(lo, hi, initial, refined)] per bin, lo / hi the edges as given, initial / refined in the get_statistics format
+    (with the truncated sub-dict when residual_threshold is given)."""
+    who = "evaluate_binned"
+    e = _bin_edges(edges, who)
+    n_bins = len(e) - 1
+    thr = _threshold(residual_threshold, who) or None
+    slope = isinstance(by, str)
+    if slope and by != "slope":
+        raise ValueError(f"{who}: by={by!r}: expected a raster or \"slope\"")
+    if slope and gsd is None:
+        raise ValueError(f"{who}: by=\"slope\" needs gsd=")
+    if slope:
+        _pair_of(gsd, f"{who}: gsd", float)
+        cut = [_degrees_to_tangent(v) for v in e]
+        if any(not a < b for a, b in zip(cut, cut[1:])):
+            raise ValueError(f"{who}: the slope edges {e} do not increase as tangents (degrees within (-90, 90))")
+    else:
+        cut = e
+        if tuple(by.shape) != tuple(gt.shape):
+            raise ValueError(f"{who}: covariate shape {tuple(by.shape)} != raster shape {tuple(gt.shape)}")
+    dev = _first_device(prediction, initial, gt, default=device)
+    r_before, r_after, cls, _ = _classified(prediction, initial, gt, area_defn, mask_gt, None, None, None, nodata, dev, who)
+    cov = _slope_tangent(_float_raster(gt, dev), gsd, nodata, who) if slope else _float_raster(by, dev)
+    n = cls.numel()
+    groups = -(-n_bins // BINS_PER_PLANE)
+    planes = torch.empty((groups, n), dtype=torch.uint8, device=dev)
+    lib = load()
+    edge_a = (ctypes.c_double * (n_bins + 1))(*cut)
+    per_bin = 4 if thr else 2                          # sets of a bin: initial, refined (each with its truncated set)
+    out = torch.empty((n_bins * per_bin, 8), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.rd_bin_classes(ptr(cov), int(cov.dtype == torch.float64), ptr(cls), n, edge_a, n_bins, ptr(planes),
+                                 stream_ptr()), "bin_classes")
+        ws = workspace(lib.rd_residual_stats_sets_ws_bytes(n, MAX_SETS), dev, slot=3)
+        for g in range(groups):
+            bins = range(g * BINS_PER_PLANE, min(n_bins, (g + 1) * BINS_PER_PLANE))
+            sets = [(src, valid | (4 << (b - g * BINS_PER_PLANE)), t) for b in bins
+                    for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)) for t in ((None, thr) if thr else (None,))]
+            row0 = bins[0] * per_bin
+            for k in range(0, len(sets), MAX_SETS):     # a call takes 20 sets
+                part = sets[k:k + MAX_SETS]
+                need_a, thr_a, src_a = _set_arrays(part)
+                check(lib.rd_residual_stats_sets(ptr(r_before), ptr(r_after), ptr(planes[g]), n, src_a, need_a, thr_a, len(part),
+                                                 ptr(out[row0 + k:row0 + k + len(part)]), ws.data_ptr(), ws.numel(),
+                                                 stream_ptr()), "residual_stats_sets")
+    rows = out.cpu().numpy()
+    step = 2 if thr else 1
+    res = []
+    for b in range(n_bins):
+        q = rows[b * per_bin:(b + 1) * per_bin]
+        res.append(AttrDict(lo=e[b], hi=e[b + 1],
+                            initial=_stats_dict(q[0], q[1] if thr else None, thr),
+                            refined=_stats_dict(q[step], q[step + 1] if thr else None, thr)))
+    return res
+
+
+def print_binned(stats, logger, unit=""):
+    """One table for the list evaluate_binned returns, in the number format of print_statistics: per bin its interval, the pixel
+    count of the refined DSM and MAE, RMSE, median and NMAD of the initial -> the refined DSM [m]."""
+    logger.info("{:>21s}\t{:>10s}\t{:>23s}\t{:>23s}\t{:>23s}\t{:>23s}".format(
+        "Bin" + (" [{}]".format(unit) if unit else ""), "Pixels", "MAE [m]", "RMSE [m]", "Median [m]", "NMAD [m]"))
+    for k, b in enumerate(stats):
+        cols = "\t".join("{:10.3f} ->{:10.3f}".format(b.initial[key], b.refined[key]) for key in ("MAE", "RMSE", "median", "NMAD"))
+        logger.info("[{:9.3f},{:9.3f})\t{:10d}\t{}{}".format(b.lo, b.hi, int(b.refined["count_total"]), cols,
+                                                            "\n" if k == len(stats) - 1 else ""))

@@ -207,6 +207,11 @@ SIGNATURES_ERRMAP = {
 }
 # the constants of that header
 CELL_MIN, CELL_MAX, BIN_MAX = 4, 256, 24
+# include/resdepth_hip_tail.h (the last convolution's skip term taken in level 0's BN / activation / pool pass), one to one as above
+SIGNATURES_TAIL = {
+    "rd_bn_act_pool_fwd_tailskip": (I, [P, P, P, P, P, F, P, P, P, P, P, P, I, I, I, I, P]),
+    "rd_conv3x3_last_fwd_tail_pre": (I, [P, P, P, P, P, I, P, I, I, I, P]),
+}
 
 
 class ProfEntry(C.Structure):
@@ -229,7 +234,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
                 + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()) \
-                + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()):
+                + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()) + list(SIGNATURES_TAIL.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

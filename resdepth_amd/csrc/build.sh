@@ -27,7 +27,8 @@ UNITS="rd_runtime rd_igemm rd_convt rd_wgrad_strip rd_elementwise rd_tiles rd_ed
 INC="$HERE/../../include"
 HEADERS=("$HERE/rd_common.h" "$HERE/rd_mfma_dev.h" "$HERE/rd_nt.h" "$HERE/rd_tile_dev.h" "$INC/resdepth_hip.h"
          "$INC/resdepth_hip_tta.h" "$INC/resdepth_hip_pairs.h" "$INC/resdepth_hip_eval.h" "$INC/resdepth_hip_loss.h"
-         "$INC/resdepth_hip_optim.h" "$INC/resdepth_hip_dist.h" "$INC/resdepth_hip_errmap.h")
+         "$INC/resdepth_hip_optim.h" "$INC/resdepth_hip_dist.h" "$INC/resdepth_hip_errmap.h"
+         "$INC/resdepth_hip_tail.h")
 pids=()
 objs=()
 for f in $UNITS; do

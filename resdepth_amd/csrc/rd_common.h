@@ -123,6 +123,11 @@ int tail_compose_launch(const float* wt, const float* bt, const float* wl, float
                         hipStream_t s);
 int conv_last_fwd_tail_launch(const TailSkip& sk, const float* t16, const float* b9, const float* wt, const float* bias,
                               const float* x_nchw, int xc, float* out, int n, int h, int w, int c, hipStream_t s);
+// the tail's skip term taken in level 0's BN / activation / pool pass, and the rest of the tail (include/resdepth_hip_tail.h)
+int bn_act_pool_tailskip_launch(const TailSkip& sk, const float* wt, float* pooled, uint8_t* idx, float* zpool, float* skip9, int n,
+                                int h, int w, int c, hipStream_t s, unsigned* p_amax);
+int conv_last_fwd_pre_launch(const float* skip9, const float* t16, const float* b9, const float* bias, const float* x_nchw, int xc,
+                             float* out, int n, int h, int w, hipStream_t s);
 int conv_last_wgrad_tail_launch(const TailSkip& sk, const float* dout, double* partial, int n, int h, int w, int c, hipStream_t s);
 int tail_t16_launch(const TailSkip& sk, const float* V, float* t16, long pixels, int cin, hipStream_t s);
 int convt_last_wgrad_launch(const float* x, const TailSkip& sk, const float* dout, const float* wl, float* dwt, double* partial,

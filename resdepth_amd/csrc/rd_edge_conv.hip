@@ -218,6 +218,243 @@ __global__ __launch_bounds__(256) void conv_last_fwd_tail_kernel(TailSkip sk, co
     }
 }
 
+// ---- the skip term of the tail, taken where z is read anyway ------------------------------------------------------------------
+// conv_last(act(BN(z)))[q] depends on z, level 0's batch statistics and the last layer's weight only, and all three exist when
+// level 0's BN / activation / pool pass runs: that pass evaluates the very act(BN(z)) per element that conv_last_fwd_tail_kernel
+// evaluates again at the end of the forward.  bn_act_pool_tailskip_kernel is both first loops in one read of z: the tile, lane
+// and V layout of the tail kernel above (so the nine tap partials and their sum are its bits), a thread owning the four pixels of
+// a 2 x 2 pooling window for its 8 channels (tile origins are even: a window never straddles tiles, pooling needs no exchange;
+// the comparison loop of bn_act_pool_fwd_kernel, so pooled / zpool / arg-max are its bits), the one-pixel ring as a ragged
+// extra round without pooling.  Out comes the one-channel skip9 [N][H][W]; conv_last_fwd_pre_kernel adds the rest of the tail.
+template <int LP>
+__device__ __forceinline__ void tap_partials_to_v(const float (&sv)[8], const float (&wr)[9][8], float* __restrict__ V, int hp,
+                                                  bool write) {
+    float pt[9];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        float a = sv[0] * wr[tap][0];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) a = fmaf(sv[k], wr[tap][k], a);
+        pt[tap] = lane_group_sum<LP>(a);
+    }
+    if (write) {
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) V[hp * EVS + tap] = pt[tap];
+    }
+}
+
+template <int LP>
+__global__ __launch_bounds__(256) void bn_act_pool_tailskip_kernel(TailSkip sk, const float* __restrict__ w,
+                                                                   float* __restrict__ pooled, uint8_t* __restrict__ idx,
+                                                                   float* __restrict__ zpool, float* __restrict__ skip9, int N,
+                                                                   int H, int W, int tiles_x, int tiles_y, unsigned* p_amax) {
+    constexpr int C = LP * 8, PPI = 256 / LP;
+    constexpr int TW2 = ET_W / 2, NWIN = (ET_H / 2) * TW2;      // 128 pooling windows per tile
+    constexpr int WR = NWIN / PPI;                              // window rounds: 4 / 2 / 1 at LP = 8 / 4 / 2
+    constexpr int NRING = EH_NP - ET_H * ET_W;                  // 100 ring pixels: rows 0 and 17, columns 0 and 33
+    constexpr int RR = (NRING + PPI - 1) / PPI;                 // ring pixels per thread: 4 / 2 / 1 (the last round is ragged)
+    __shared__ float V[EH_NP * EVS];
+    const int t = threadIdx.x, q = t % LP, slot = t / LP;
+    const int tl = blockIdx.x;
+    const int tx = tl % tiles_x, ty = (tl / tiles_x) % tiles_y, n = tl / (tiles_x * tiles_y);
+    const int y0 = ty * ET_H, x0 = tx * ET_W;
+    float wr[9][8];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wr[tap][k] = w[(q * 8 + k) * 9 + tap];
+    float sc[8], sh[8];
+    const float slope = sk.slope_dev ? sk.slope_dev[0] : sk.slope;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int c = q * 8 + k;
+        sc[k] = sk.invstd[c] * sk.gamma[c];
+        sh[k] = sk.beta[c] - sk.mean[c] * sc[k];
+    }
+    // one descriptor per image (H * W * C * 4 < 2^31, checked by the entry point: byte offsets fit an int); a masked lane carries an out-of-extent
+    // offset and reads zeros -- no branch around a load
+    const __amdgpu_buffer_rsrc_t rsZ = make_rsrc(sk.z + (long)n * H * W * C, (unsigned)((long)H * W * C * 4));
+    const int H2 = H >> 1, W2 = W >> 1;
+    float pmx = 0.f;
+    // round r < WR: the thread's r-th window (four pixels); round WR: its RR <= 4 ring pixels.  The loads of round r + 1 are
+    // issued before round r is evaluated (two register buffers): a wave always has a round of z in flight
+    auto load_window = [&](int r, float4 (&v)[4][2]) {
+        const int wi = r * PPI + slot, wy = wi / TW2, wx = wi - wy * TW2;
+        const int gy = y0 + 2 * wy, gx = x0 + 2 * wx;
+        const bool ok = gy < H && gx < W;           // H, W even: all four pixels of the window or none
+        const unsigned base = (unsigned)(((gy * W + gx) * C + q * 8) * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned off = ok ? base + (unsigned)((((k >> 1) * W + (k & 1)) * C) * 4) : kOOB;
+            // no streaming hint, unlike bn_act_pool_fwd_kernel: a tile's border pixels are its neighbours' ring, read within
+            // microseconds, and must stay in L2 for them (with the hint: 194 instead of 186 us at cfg-S)
+            v[k][0] = buf_load4(rsZ, off, 0);
+            v[k][1] = buf_load4(rsZ, off + 16u, 0);
+        }
+    };
+    auto ring_pixel = [&](int u, int& hp, bool& in, unsigned& off) {
+        const int ri = u * PPI + slot;
+        int hy, hx;
+        if (ri < EH_W) hy = 0, hx = ri;
+        else if (ri < 2 * EH_W) hy = EH_H - 1, hx = ri - EH_W;
+        else if (ri < 2 * EH_W + ET_H) hy = 1 + ri - 2 * EH_W, hx = 0;
+        else hy = 1 + ri - 2 * EH_W - ET_H, hx = EH_W - 1;
+        hp = ri < NRING ? hy * EH_W + hx : -1;
+        const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+        in = ri < NRING && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+        off = in ? (unsigned)(((gy * W + gx) * C + q * 8) * 4) : kOOB;
+    };
+    auto load_ring = [&](float4 (&v)[4][2]) {
+#pragma unroll
+        for (int u = 0; u < RR; ++u) {
+            int hp;
+            bool in;
+            unsigned off;
+            ring_pixel(u, hp, in, off);
+            v[u][0] = buf_load4(rsZ, off, 0);
+            v[u][1] = buf_load4(rsZ, off + 16u, 0);
+        }
+    };
+    auto eval_window = [&](int r, const float4 (&v)[4][2]) {
+        const int wi = r * PPI + slot, wy = wi / TW2, wx = wi - wy * TW2;
+        const int gy = y0 + 2 * wy, gx = x0 + 2 * wx;
+        const bool ok = gy < H && gx < W;
+        float m[8], zm[8];
+        int mi[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float zv[8] = {v[k][0].x, v[k][0].y, v[k][0].z, v[k][0].w, v[k][1].x, v[k][1].y, v[k][1].z, v[k][1].w};
+            float sv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float y = fmaf(zv[j], sc[j], sh[j]);
+                const float a = y > 0.f ? y : y * slope;
+                // torch max_pool2d: (val > maxval) || isnan(val) replaces -> first max wins, NaN wins
+                if (k == 0 || a > m[j] || a != a) {
+                    m[j] = a;
+                    mi[j] = k;
+                    zm[j] = zv[j];
+                }
+                sv[j] = ok ? a : 0.f;               // tile overhang: the activation outside the image is 0
+            }
+            tap_partials_to_v<LP>(sv, wr, V, (2 * wy + (k >> 1) + 1) * EH_W + 2 * wx + (k & 1) + 1, q == 0);
+        }
+        if (ok) {
+            const long o = (((long)n * H2 + (gy >> 1)) * W2 + (gx >> 1)) * C + q * 8;
+            *reinterpret_cast<float4*>(pooled + o) = make_float4(m[0], m[1], m[2], m[3]);
+            *reinterpret_cast<float4*>(pooled + o + 4) = make_float4(m[4], m[5], m[6], m[7]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pmx = amax_acc(pmx, m[j]);
+            if (zpool) {                            // read in the backward
+                st_nt4(zpool + o, make_float4(zm[0], zm[1], zm[2], zm[3]));
+                st_nt4(zpool + o + 4, make_float4(zm[4], zm[5], zm[6], zm[7]));
+            }
+            st_nt_u8x4(idx + o, make_uchar4((unsigned char)mi[0], (unsigned char)mi[1], (unsigned char)mi[2], (unsigned char)mi[3]));
+            st_nt_u8x4(idx + o + 4, make_uchar4((unsigned char)mi[4], (unsigned char)mi[5], (unsigned char)mi[6], (unsigned char)mi[7]));
+        }
+    };
+    // the ring: neighbouring tiles' pixels (or the zero padding), tap partials only
+    auto eval_ring = [&](const float4 (&v)[4][2]) {
+#pragma unroll
+        for (int u = 0; u < RR; ++u) {
+            int hp;
+            bool in;
+            unsigned off;
+            ring_pixel(u, hp, in, off);
+            float sv[8] = {v[u][0].x, v[u][0].y, v[u][0].z, v[u][0].w, v[u][1].x, v[u][1].y, v[u][1].z, v[u][1].w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {          // zero padding applies to the ACTIVATION: pixels outside stay 0
+                const float y = fmaf(sv[j], sc[j], sh[j]);
+                sv[j] = in ? (y > 0.f ? y : y * slope) : 0.f;
+            }
+            tap_partials_to_v<LP>(sv, wr, V, hp, q == 0 && hp >= 0);
+        }
+    };
+    float4 va[4][2], vb[4][2];
+    load_window(0, va);
+#pragma unroll
+    for (int r = 0; r < WR; r += 2) {
+        if (r + 1 < WR) load_window(r + 1, vb);
+        else load_ring(vb);
+        eval_window(r, va);
+        if (r + 1 < WR) {
+            if (r + 2 < WR) load_window(r + 2, va);
+            else load_ring(va);
+            eval_window(r + 1, vb);
+        }
+    }
+    eval_ring(WR % 2 ? vb : va);
+    __syncthreads();
+    for (int e = t; e < ET_H * ET_W; e += 256) {
+        const int py = e / ET_W, px = e - py * ET_W;
+        const int gy = y0 + py, gx = x0 + px;
+        if (gy >= H || gx >= W) continue;
+        float acc = 0.f;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) acc += V[((py + tap / 3) * EH_W + px + tap % 3) * EVS + tap];
+        skip9[((long)n * H + gy) * W + gx] = acc;
+    }
+    if (p_amax) amax_commit(p_amax, pmx);       // one commit per block; a tile is a contiguous piece of the pooled tensor's rows
+}
+
+// out = ((skip9 + up) + bsum) + bias (+ x[:, 0]): the second loop of conv_last_fwd_tail_kernel, association and order kept, with
+// the sum of the nine tap partials read instead of formed -- the same bits.  One thread per output pixel; the grid is
+// (columns / 64, rows / 4, images) over blocks of 64 x 4 threads, so no index is divided and a wave covers 256 contiguous bytes.
+// The 4 x 34 coarse pixels of T a block touches come in as 16-byte loads and wait in LDS (pitch 17: the four values a pixel
+// takes lie 16 floats apart in T, a 16-way bank conflict at pitch 16, and 4-byte gathers from global memory took twice as long).
+constexpr int PRE_W = 64, PRE_H = 4, PRE_CW = PRE_W / 2 + 2, PRE_CH = PRE_H / 2 + 2, PRE_P = 17;
+__global__ __launch_bounds__(256) void conv_last_fwd_pre_kernel(const float* __restrict__ skip9, const float* __restrict__ t16,
+                                                                const float* __restrict__ b9, const float* __restrict__ bias,
+                                                                const float* __restrict__ x_nchw, int xc, float* __restrict__ out,
+                                                                int H, int W) {
+    __shared__ float T[PRE_CH * PRE_CW * PRE_P];
+    const int gx = blockIdx.x * PRE_W + threadIdx.x, gy = blockIdx.y * PRE_H + threadIdx.y;
+    const long n = blockIdx.z;
+    const int Hc = H >> 1, Wc = W >> 1;
+    const int cy0 = blockIdx.y * (PRE_H / 2) - 1, cx0 = blockIdx.x * (PRE_W / 2) - 1;
+    for (int e = threadIdx.y * PRE_W + threadIdx.x; e < PRE_CH * PRE_CW * 4; e += 256) {
+        const int f = e & 3, cp = e >> 2, ry = cp / PRE_CW, rx = cp - ry * PRE_CW;
+        const int cy = cy0 + ry, cx = cx0 + rx;
+        if ((unsigned)cy < (unsigned)Hc && (unsigned)cx < (unsigned)Wc) {      // (pixels outside are never looked up below)
+            const float4 v = *reinterpret_cast<const float4*>(t16 + ((n * Hc + cy) * Wc + cx) * 16 + f * 4);
+            float* d = T + cp * PRE_P + f * 4;
+            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+        }
+    }
+    __syncthreads();
+    if (gx >= W || gy >= H) return;
+    const long e = (n * H + gy) * W + gx;
+    const float b0 = bias ? bias[0] : 0.f;
+    float acc = skip9[e];
+    // up-convolution part: q even -> (p', d) = (q/2, 0), (q/2 - 1, 2); q odd -> ((q-1)/2, 1), ((q+1)/2, -1)
+    float up = 0.f;
+#pragma unroll
+    for (int jy = 0; jy < 2; ++jy) {
+        const int cy = (gy >> 1) + ((gy & 1) ? jy : -jy), dy = (gy & 1) ? (jy ? -1 : 1) : (jy ? 2 : 0);
+        if ((unsigned)cy >= (unsigned)Hc) continue;
+#pragma unroll
+        for (int jx = 0; jx < 2; ++jx) {
+            const int cx = (gx >> 1) + ((gx & 1) ? jx : -jx), dx = (gx & 1) ? (jx ? -1 : 1) : (jx ? 2 : 0);
+            if ((unsigned)cx >= (unsigned)Wc) continue;
+            up += T[((cy - cy0) * PRE_CW + cx - cx0) * PRE_P + (dy + 1) * 4 + dx + 1];
+        }
+    }
+    float bsum = 0.f;
+    if (gy > 0 && gy < H - 1 && gx > 0 && gx < W - 1) {       // away from the border: all nine, in the same order (uniform values)
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) bsum += b9[tap];
+    } else {
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ry = gy + tap / 3 - 1, rx = gx + tap % 3 - 1;
+            if ((unsigned)ry < (unsigned)H && (unsigned)rx < (unsigned)W) bsum += b9[tap];
+        }
+    }
+    acc = ((acc + up) + bsum) + b0;
+    if (x_nchw) acc = x_nchw[((n * xc) * H + gy) * W + gx] + acc;
+    out[e] = acc;
+}
+
 // dout tile (+ one-pixel halo, zero outside the image) -> LDS; D[hy][hx] = dout[y0 - 1 + hy][x0 - 1 + hx]
 __device__ __forceinline__ void load_dout_tile(float* D, const float* __restrict__ dout, int n, int y0, int x0, int H, int W,
                                                int t) {
@@ -1788,6 +2025,24 @@ int conv_last_fwd_tail_launch(const TailSkip& sk, const float* t16, const float*
     else if (c == 32) RD_LAUNCH(conv_last_fwd_tail_kernel<4>, grid, dim3(256), 0, s, sk, t16, b9, wt, bias, x_nchw, xc, out, n, h, w, tx, ty);
     else RD_LAUNCH(conv_last_fwd_tail_kernel<2>, grid, dim3(256), 0, s, sk, t16, b9, wt, bias, x_nchw, xc, out, n, h, w, tx, ty);
     RD_LAUNCH_CHECK("conv_last_fwd_tail");
+    return RD_OK;
+}
+
+int bn_act_pool_tailskip_launch(const TailSkip& sk, const float* wt, float* pooled, uint8_t* idx, float* zpool, float* skip9, int n,
+                                int h, int w, int c, hipStream_t s, unsigned* p_amax) {
+    const int tx = cdiv(w, ET_W), ty = cdiv(h, ET_H);
+    const dim3 grid(n * tx * ty);
+    if (c == 64) RD_LAUNCH(bn_act_pool_tailskip_kernel<8>, grid, dim3(256), 0, s, sk, wt, pooled, idx, zpool, skip9, n, h, w, tx, ty, p_amax);
+    else if (c == 32) RD_LAUNCH(bn_act_pool_tailskip_kernel<4>, grid, dim3(256), 0, s, sk, wt, pooled, idx, zpool, skip9, n, h, w, tx, ty, p_amax);
+    else RD_LAUNCH(bn_act_pool_tailskip_kernel<2>, grid, dim3(256), 0, s, sk, wt, pooled, idx, zpool, skip9, n, h, w, tx, ty, p_amax);
+    RD_LAUNCH_CHECK("bn_act_pool_tailskip");
+    return RD_OK;
+}
+
+int conv_last_fwd_pre_launch(const float* skip9, const float* t16, const float* b9, const float* bias, const float* x_nchw, int xc,
+                             float* out, int n, int h, int w, hipStream_t s) {
+    RD_LAUNCH(conv_last_fwd_pre_kernel, dim3(cdiv(w, 64), cdiv(h, 4), n), dim3(64, 4), 0, s, skip9, t16, b9, bias, x_nchw, xc, out, h, w);
+    RD_LAUNCH_CHECK("conv_last_fwd_pre");
     return RD_OK;
 }
 

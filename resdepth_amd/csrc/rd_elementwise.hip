@@ -1594,6 +1594,34 @@ int rd_conv3x3_last_fwd_tail(const float* z, const float* mean, const float* inv
     return conv_last_fwd_tail_launch(sk, t16, b9, w_last, bias, x_nchw, x_channels, out, n, h, w, c, (hipStream_t)s);
 }
 
+int rd_bn_act_pool_fwd_tailskip(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                float slope, const float* slope_dev, const float* w_last, float* pooled, uint8_t* idx, float* zpool,
+                                float* skip9, int n, int h, int w, int c, rd_stream_t s) {
+    RD_REQUIRE(z && mean && invstd && gamma && beta && w_last && pooled && idx && skip9,
+               "rd_bn_act_pool_fwd_tailskip: null pointer");
+    RD_REQUIRE(n > 0 && h > 0 && w > 0 && (c == 16 || c == 32 || c == 64) && h % 2 == 0 && w % 2 == 0,
+               "rd_bn_act_pool_fwd_tailskip: C in {16, 32, 64}, H and W even (got %d, %dx%d)", c, h, w);
+    RD_REQUIRE((long)h * w * c * 4 < (1L << 31), "rd_bn_act_pool_fwd_tailskip: an image of z must stay below 2 GiB (got %dx%dx%d)",
+               h, w, c);
+    const QuantArgs qa = quant_take();      // out2: magnitude slot of pooled, as in rd_bn_act_pool_fwd
+    const TailSkip sk = {z, mean, invstd, gamma, beta, slope_dev, slope};
+    const double pixels = (double)n * h * w;
+    ProfScope ps((hipStream_t)s, "bn_act_pool_tailskip", 2.0 * pixels * 9.0 * c,
+                 4.0 * pixels * c * 1.25 + 0.25 * pixels * c + (zpool ? 1.0 * pixels * c : 0.0) + 4.0 * pixels);
+    return bn_act_pool_tailskip_launch(sk, w_last, pooled, idx, zpool, skip9, n, h, w, c, (hipStream_t)s, qa.out2);
+}
+
+int rd_conv3x3_last_fwd_tail_pre(const float* skip9, const float* t16, const float* b9, const float* bias, const float* x_nchw,
+                                 int x_channels, float* out, int n, int h, int w, rd_stream_t s) {
+    RD_REQUIRE(skip9 && t16 && b9 && out, "rd_conv3x3_last_fwd_tail_pre: null pointer");
+    RD_REQUIRE(n > 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && (!x_nchw || x_channels > 0),
+               "rd_conv3x3_last_fwd_tail_pre: H and W even, x_channels > 0 with x (got %dx%d, %d)", h, w, x_channels);
+    RD_REQUIRE(n <= 65535 && h <= 4 * 65535, "rd_conv3x3_last_fwd_tail_pre: at most 65535 images of at most 262140 rows (got %d, %d)",
+               n, h);
+    ProfScope ps((hipStream_t)s, "conv_last_fwd_pre", 0, 4.0 * n * h * w * (double)(1 + 4 + (x_nchw ? 1 : 0) + 1));
+    return conv_last_fwd_pre_launch(skip9, t16, b9, bias, x_nchw, x_channels, out, n, h, w, (hipStream_t)s);
+}
+
 int rd_conv3x3_last_bwd_tail_blocks(int n, int h, int w) { return conv_last_tail_blocks(n, h, w); }
 
 int rd_conv3x3_last_bwd_tail_fused(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta,

@@ -368,6 +368,17 @@ def conv3x3_last_fwd_tail(skip, t16, b9, w_last, bias, x_nchw):
     return out
 
 
+def conv3x3_last_fwd_tail_pre(skip9, t16, b9, bias, x_nchw):
+    """The rest of conv3x3_last_fwd_tail when its skip term skip9 [N, H, W] came out of bn_act_pool_fwd_tailskip
+    (include/resdepth_hip_tail.h: rd_conv3x3_last_fwd_tail_pre) -- the same bits, without reading z again."""
+    n, h, wd_ = skip9.shape
+    out = torch.empty(n, 1, h, wd_, device=skip9.device, dtype=torch.float32)
+    xc = x_nchw.shape[1] if x_nchw is not None else 0
+    check(load().rd_conv3x3_last_fwd_tail_pre(ptr(skip9), ptr(t16), ptr(b9), ptr(bias.detach() if bias is not None else None),
+                                              ptr(x_nchw), xc, ptr(out), n, h, wd_, stream_ptr()), "conv3x3_last_fwd_tail_pre")
+    return out
+
+
 def conv3x3_last_bwd_tail_fused(skip, dout, w_last):
     """One pass over level 0's z at the head of the backward: -> (wpartial, (BN-backward partial rows, count)) -- the partial
     sums of the last convolution's weight gradient (tail_wl_finish completes them) and the statistics of the level-0 hook."""
@@ -656,6 +667,24 @@ def bn_act_pool_fwd(z, mean, invstd, gamma, beta, slope, pool, slope_dev=None, w
     if want_zpool:
         return a, pooled, idx, zpool
     return a, pooled, idx
+
+
+def bn_act_pool_fwd_tailskip(z, mean, invstd, gamma, beta, slope, w_last, slope_dev=None, want_zpool=False):
+    """bn_act_pool_fwd(pool=True, want_a=False) that also emits the last convolution's skip term from the values it holds:
+    -> (pooled, idx, zpool | None, skip9 [N, H, W]) with skip9 = conv_last(act(BN(z))) before bias, up-convolution part and
+    residual (include/resdepth_hip_tail.h: rd_bn_act_pool_fwd_tailskip).  C in {16, 32, 64}, H and W even."""
+    n, h, w, c = z.shape
+    pooled = torch.empty(n, h // 2, w // 2, c, device=z.device, dtype=torch.float32)
+    idx = torch.empty(n, h // 2, w // 2, c, device=z.device, dtype=torch.uint8)
+    zpool = torch.empty_like(pooled) if want_zpool else None
+    skip9 = torch.empty(n, h, w, device=z.device, dtype=torch.float32)
+    sp = _out_slot()
+    quant_next(out2=sp)
+    tag(pooled, sp)
+    check(load().rd_bn_act_pool_fwd_tailskip(ptr(z), ptr(mean), ptr(invstd), ptr(gamma.detach()), ptr(beta.detach()),
+                                             float(slope), ptr(slope_dev), ptr(w_last.detach()), ptr(pooled), ptr(idx),
+                                             ptr(zpool), ptr(skip9), n, h, w, c, stream_ptr()), "bn_act_pool_fwd_tailskip")
+    return pooled, idx, zpool, skip9
 
 
 def bn_act_bwd_reduce(z, mean, invstd, gamma, beta, slope, g_full, g_pool, idx, slope_dev=None, dgamma=None, dbeta=None,

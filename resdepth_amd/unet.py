@@ -148,6 +148,7 @@ class UNet(nn.Module):
         self.fused_bn_bwd_stats = True    # BN-backward sums from the epilogues of the kernels producing the gradient operands
         self.composed_tail = True         # last up-convolution's gradients straight from the 1-channel dout (ops.tail_*)
         self.fused_first_wgrad = True     # level 0: BN / activation / pool backward evaluated inside the first conv's weight gradient
+        self.fold_tail_skip = True        # level 0's BN / activation / pool pass also emits the last convolution's skip term: the tail does not read z0 again
         self.fused_first_eval = True      # inference: level 0's BN + activation + max-pool inside the first convolution (no z0)
         self.fast_eval = False            # inference with ONE scale per tensor (as in training): results then depend on the batch composition in the last bits
         self.eval_per_image = True        # inference on the three-product (split2h) bodies with one scale per IMAGE: a tile's result depends on that tile alone (False: six-product bodies, r01-r05)
@@ -493,7 +494,22 @@ class UNet(nn.Module):
         else:
             _, v, _, b9 = ops.tail_compose(up.weight, self.last_layer.weight, up.bias, forward=True)
         # cur: the up-convolution's input, or the lazy descriptor of the block that produces it (BN + activation on load)
-        return {"skip": skip, "t16": ops.tail_t16(cur, v), "b9": b9, "v": v}
+        # skip9 (fold_tail_skip): the last convolution's skip term, already formed by level 0's pool pass; it moves from the
+        # descriptor into the tail record and leaves that with its one use (the backward reads z0, not skip9)
+        return {"skip": skip, "t16": ops.tail_t16(cur, v), "b9": b9, "v": v, "skip9": skip.pop("skip9", None)}
+
+    def _tail_out(self, tail, x_res):
+        """The end of the forward on the composed tail: from skip9 when level 0 emitted it, else from z0 (the same bits)."""
+        ll = self.last_layer
+        skip9 = tail.pop("skip9", None)
+        if skip9 is not None:
+            return ops.conv3x3_last_fwd_tail_pre(skip9, tail["t16"], tail["b9"], ll.bias, x_res)
+        return ops.conv3x3_last_fwd_tail(tail["skip"], tail["t16"], tail["b9"], ll.weight, ll.bias, x_res)
+
+    def _fold_tail_expected(self, z, lazy_skip: bool) -> bool:
+        """Does level 0's pool pass (z = z0 [N, H, W, C0]) also form the tail's skip term?"""
+        return bool(self.fold_tail_skip and self._tail_expected(lazy_skip) and z.shape[-1] in (16, 32, 64)
+                    and z.shape[1] % 2 == 0 and z.shape[2] % 2 == 0)
 
     def _tail_expected(self, lazy_skip: bool) -> bool:
         """Will the forward take the composed tail (then the block feeding the last up-convolution need not write its
@@ -538,20 +554,32 @@ class UNet(nn.Module):
             return 0.0, slope.detach()
         return slope, None
 
-    def _bn_forward(self, z, bn, slope, pool, training, sums=None, bias=None, want_a=True, stats=None, want_zpool=False):
+    def _bn_forward(self, z, bn, slope, pool, training, sums=None, bias=None, want_a=True, stats=None, want_zpool=False,
+                    tail_w=None):
         """-> (a | skip descriptor, pooled, idx, mean, invstd, count[, zpool]).  want_a=False (pooled levels): the full-resolution
         activation is not written; the first return value is then the descriptor the transposed convolution needs to
-        recompute it from z in its epilogue."""
+        recompute it from z in its epilogue.  tail_w (level 0 with pool and want_a=False, `_fold_tail_expected`): the last
+        convolution's weight -- the pool pass also forms the tail's skip term, the descriptor carries it as "skip9"."""
         c = z.shape[-1]
         slope, sdev = self._split_slope(slope)
+
+        def act_pool(mean, invstd, gamma, beta):
+            if tail_w is None:
+                return ops.bn_act_pool_fwd(z, mean, invstd, gamma, beta, slope, pool, sdev, want_a=want_a, want_zpool=want_zpool)
+            assert pool and not want_a
+            p_, idx_, zp_, skip9 = ops.bn_act_pool_fwd_tailskip(z, mean, invstd, gamma, beta, slope, tail_w, sdev,
+                                                                want_zpool=want_zpool)
+            a_ = {"z": z, "mean": mean, "invstd": invstd, "gamma": gamma, "beta": beta, "slope": slope, "slope_dev": sdev,
+                  "skip9": skip9}
+            return (a_, p_, idx_, zp_) if want_zpool else (a_, p_, idx_)
+
         if bn is None:
             # do_BN=False: activation(conv + bias) == the fused BN-apply kernel with mean 0, invstd 1, gamma 1, beta = bias
             mean, invstd = self._const(c, 0.0, z.device), self._const(c, 1.0, z.device)
             if not pool and not want_a:
                 return ({"z": z, "mean": mean, "invstd": invstd, "gamma": invstd, "beta": bias, "slope": slope, "slope_dev": sdev},
                         None, None, mean, invstd, 1)
-            a, p, idx, *zp = ops.bn_act_pool_fwd(z, mean, invstd, invstd, bias, slope, pool, sdev, want_a=want_a,
-                                                 want_zpool=want_zpool)
+            a, p, idx, *zp = act_pool(mean, invstd, invstd, bias)
             if a is None:
                 a = {"z": z, "mean": mean, "invstd": invstd, "gamma": invstd, "beta": bias, "slope": slope, "slope_dev": sdev}
             return (a, p, idx, mean, invstd, 1, *zp)
@@ -572,8 +600,7 @@ class UNet(nn.Module):
         if not pool and not want_a:          # nothing to compute: the consumers evaluate act(BN(z)) on load (the composed tail)
             a = {"z": z, "mean": mean, "invstd": invstd, "gamma": bn.weight, "beta": bn.bias, "slope": slope, "slope_dev": sdev}
             return (a, None, None, mean, invstd, count)
-        a, p, idx, *zp = ops.bn_act_pool_fwd(z, mean, invstd, bn.weight, bn.bias, slope, pool, sdev, want_a=want_a,
-                                             want_zpool=want_zpool)
+        a, p, idx, *zp = act_pool(mean, invstd, bn.weight, bn.bias)
         if a is None:
             a = {"z": z, "mean": mean, "invstd": invstd, "gamma": bn.weight, "beta": bn.bias, "slope": slope, "slope_dev": sdev}
         return (a, p, idx, mean, invstd, count, *zp)
@@ -736,9 +763,12 @@ class UNet(nn.Module):
             # transposed up-mode: the skip activation is recomputed from z in the decoder's convT epilogue, not stored
             lazy_skip = self.up_mode == "transpose" and not keep_skips
             want_zp = save and self.fused_bn_bwd_stats
+            # level 0 on the composed tail: the pool pass also forms the last convolution's skip term (z0 is not read again)
+            fold = i == 0 and self._fold_tail_expected(z, lazy_skip)
             a, p, idx, mean, invstd, count, *zp = self._bn_forward(z, bn, self._act_of(blk, self.act_fn_encoder), True,
                                                                    training, sums, cbias, want_a=not lazy_skip, stats=st,
-                                                                   want_zpool=want_zp)
+                                                                   want_zpool=want_zp,
+                                                                   tail_w=self.last_layer.weight if fold else None)
             skips.append(a)
             if save:
                 S["enc"].append({"z": z, "idx": idx, "mean": mean, "invstd": invstd, "count": count, "p": p,
@@ -787,7 +817,7 @@ class UNet(nn.Module):
             if save:
                 S["outer_bn"] = obn
         if tail is not None:
-            out = ops.conv3x3_last_fwd_tail(tail["skip"], tail["t16"], tail["b9"], self.last_layer.weight, self.last_layer.bias, x_res)
+            out = self._tail_out(tail, x_res)
         else:
             out = ops.conv3x3_last_fwd(cur, self.last_layer.weight, self.last_layer.bias, x_res)
         return out, S

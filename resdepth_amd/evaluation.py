@@ -15,13 +15,12 @@ from ._lib import check, load, ptr, stream_ptr, workspace
 _KEYS = ["count_total", "diff_max", "diff_min", "MAE", "RMSE", "absolute_median", "median", "NMAD"]
 
 
-def _stats(raster, gt, mask, nodata, thr, dev):
+def _stats(raster, gt, mask, nodata, thr, out):
+    """rd_residual_stats (the single-set engine) into `out`, a device row of eight, enqueued only."""
     n = raster.numel()
-    out = torch.empty(8, dtype=torch.float64, device=dev)
-    ws = workspace(load().rd_residual_stats_ws_bytes(n), dev, slot=2)
+    ws = workspace(load().rd_residual_stats_ws_bytes(n), out.device, slot=2)
     check(load().rd_residual_stats(ptr(raster), ptr(gt), ptr(mask), n, float(nodata), float(thr if thr else -1.0), ptr(out),
                                    ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats")
-    return out
 
 
 def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=None, device="cuda", *, abs_quantiles=None,
@@ -33,9 +32,12 @@ def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=N
     dist = _dist_options(abs_quantiles, quantiles, within)
     r, g = _on(raster, dev, torch.float64), _on(raster_gt, dev, torch.float32)
     m = None if mask_gt is None else _on(mask_gt, dev).to(torch.uint8).contiguous()
+    thr = residual_threshold
+    sets = [(0, 1, t) for t in _variants(thr)]
+    rows = _Rows(len(sets), dist, r.device)
     with torch.cuda.device(r.device):              # raw launches go to the current device's stream
-        full = _stats(r, g, m, nodata, None, r.device)
-        trunc = _stats(r, g, m, nodata, residual_threshold, r.device) if residual_threshold else None
+        for out, (_, _, t) in zip(rows.stats, sets):
+            _stats(r, g, m, nodata, t, out)        # the eight numbers stay with the single-set engine
         if dist is not None:
             # the sets form over the residual and validity of residual_kernel (d = a - (double)g; valid = both != nodata,
             # under the mask), built here; the truncated set is its second set
@@ -43,21 +45,13 @@ def get_statistics(raster, raster_gt, nodata, mask_gt=None, residual_threshold=N
             ok = (r != nodata) & (gd != nodata)
             if m is not None:
                 ok &= m != 0
-            sets = [(0, 1, None)] + ([(0, 1, residual_threshold)] if residual_threshold else [])
-            drows = torch.empty((len(sets), dist.width), dtype=torch.float64, device=r.device)
-            _queue_dist_sets((r - gd).reshape(-1), None, ok.to(torch.uint8).reshape(-1), sets, dist, drows)
-    vals = full.cpu().tolist()
-    stats = {"truncation": bool(residual_threshold)}
-    stats.update(dict(zip(_KEYS, vals)))
-    if trunc is not None:
-        tv = trunc.cpu().tolist()
-        stats["truncated"] = {"count_total": tv[0], "threshold": residual_threshold, "MAE": tv[3], "RMSE": tv[4],
-                              "absolute_median": tv[5], "median": tv[6], "NMAD": tv[7]}
-    if dist is not None:
-        drows = drows.cpu().numpy()
-        dist.fill(stats, drows[0])
-        if trunc is not None:
-            dist.fill(stats["truncated"], drows[1])
+            rows.sets((r - gd).reshape(-1), None, ok.to(torch.uint8).reshape(-1), sets, quantiles_only=True)
+    full, trunc = _full_and_truncated(rows.host(), 0, thr)
+    stats = {"truncation": bool(thr)}              # a plain dict in the reference's key order, not _stats_dict's
+    stats.update(zip(_KEYS, (float(v) for v in full)))
+    if thr:
+        stats["truncated"] = dict(_truncated_dict(trunc, thr, dist))
+    _fill(dist, stats, full)
     return stats
 
 
@@ -212,60 +206,99 @@ def _dist_options(abs_quantiles, quantiles, within):
     return _Dist(abs_q, q, w) if abs_q or q or w else None
 
 
-def _queue_dist_sets(src0, src1, cls, sets, dist, out):
-    """rd_residual_dist_sets over the sets of _run_sets into out [len(sets), dist.width] (device), enqueued only."""
-    n, ns = cls.numel(), len(sets)
-    lib = load()
-    need_a, thr_a, src_a = _set_arrays(sets)
-    ws = workspace(lib.rd_residual_dist_sets_ws_bytes(n, ns, dist.n_q, dist.n_t), out.device, slot=4)
-    check(lib.rd_residual_dist_sets(ptr(src0), ptr(src1), ptr(cls), n, src_a, need_a, thr_a, ns, dist.q_a, dist.mode_a,
-                                    dist.n_q, dist.tau_a, dist.n_t, ptr(out), ws.data_ptr(), ws.numel(), stream_ptr()),
-          "residual_dist_sets")
+def _variants(thr):
+    """The thresholds of a set and, under a threshold, of its truncated set: sets are built, and their rows walked, in such
+    (full, truncated) steps."""
+    return (None, thr) if thr else (None,)
 
 
-def _run_sets(src0, src1, cls, sets, dev, dist=None):
-    """sets: [(source, need bits, threshold or None)] -> host float64 array [len(sets), 8] (rd_residual_stats_sets); with
-    dist, (that, [len(sets), dist.width] of rd_residual_dist_sets): both enqueued, one device buffer, one read-back."""
-    n, ns = cls.numel(), len(sets)
-    lib = load()
-    need_a, thr_a, src_a = _set_arrays(sets)
-    buf = torch.empty(ns * (8 + (dist.width if dist else 0)), dtype=torch.float64, device=dev)
-    out = buf[:ns * 8].view(ns, 8)
-    with torch.cuda.device(dev):
-        ws = workspace(lib.rd_residual_stats_sets_ws_bytes(n, ns), dev, slot=3)
-        check(lib.rd_residual_stats_sets(ptr(src0), ptr(src1), ptr(cls), n, src_a, need_a, thr_a, ns, ptr(out),
-                                         ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats_sets")
-        if dist is None:
-            return out.cpu().numpy()
-        _queue_dist_sets(src0, src1, cls, sets, dist, buf[ns * 8:].view(ns, dist.width))
-        host = buf.cpu().numpy()
-        return host[:ns * 8].reshape(ns, 8), host[ns * 8:].reshape(ns, dist.width)
+def _full_and_truncated(rows, q, thr):
+    """-> (the full row, the truncated row or None) of the q-th set of rows laid out in _variants steps"""
+    step = len(_variants(thr))
+    return rows[q * step], (rows[q * step + 1] if thr else None)
 
 
-def _stats_dict(full, trunc, thr, dist=None, dfull=None, dtrunc=None):
-    """rows of rd_residual_stats_sets [and of rd_residual_dist_sets] -> the reference's get_statistics dict [with the
-    abs_quantile / quantile / within keys of the options given, in the truncated sub-dict too]."""
-    st = AttrDict(truncation=bool(thr))
-    if thr:
-        st.truncated = AttrDict(count_total=float(trunc[0]), threshold=thr, MAE=float(trunc[3]), RMSE=float(trunc[4]),
-                                absolute_median=float(trunc[5]), median=float(trunc[6]), NMAD=float(trunc[7]))
-        if dist is not None:
-            dist.fill(st.truncated, dtrunc)
-    st.update(zip(_KEYS, (float(v) for v in full)))
+class _Rows:
+    """The result rows of one evaluation call: ONE float64 device buffer -- the [n_rows, 8] block the statistics kernels write
+    and behind it the [n_rows, dist.width] block of the quantile kernels (width 0 without options, and then nothing is
+    queued for it) -- filled in the order the sets are queued and read back once."""
+
+    def __init__(self, n_rows, dist, dev):
+        self.dist, self.dev, self.n_rows, self.used = dist, dev, n_rows, 0
+        self.width = dist.width if dist is not None else 0
+        self.buf = torch.empty(n_rows * (8 + self.width), dtype=torch.float64, device=dev)
+        self.stats = self.buf[:n_rows * 8].view(n_rows, 8)
+        self.quant = self.buf[n_rows * 8:].view(n_rows, self.width)
+
+    def _queue(self, stats, quant, n, args):
+        """Entry point rd_<stats> (None: left out) and, with options, rd_<quant> with `args`, which end in the set arrays and the
+        number of sets, into the next rows; enqueued only."""
+        lib, dist, ns = load(), self.dist, args[-1]
+        r0, self.used = self.used, self.used + ns
+        if self.used > self.n_rows:
+            raise RuntimeError(f"evaluate: {self.used} result rows queued into a buffer of {self.n_rows}")
+        with torch.cuda.device(self.dev):
+            if stats is not None:
+                ws = workspace(getattr(lib, f"rd_{stats}_ws_bytes")(n, ns), self.dev, slot=3)
+                check(getattr(lib, "rd_" + stats)(*args, ptr(self.stats[r0:self.used]), ws.data_ptr(), ws.numel(), stream_ptr()),
+                      stats)
+            if dist is not None:
+                ws = workspace(getattr(lib, f"rd_{quant}_ws_bytes")(n, ns, dist.n_q, dist.n_t), self.dev, slot=4)
+                check(getattr(lib, "rd_" + quant)(*args, dist.q_a, dist.mode_a, dist.n_q, dist.tau_a, dist.n_t,
+                                                  ptr(self.quant[r0:self.used]), ws.data_ptr(), ws.numel(), stream_ptr()), quant)
+
+    def sets(self, src0, src1, cls, sets, quantiles_only=False):
+        """sets: [(source, need bits, threshold or None)] over the sources and the class byte -> len(sets) rows
+        (rd_residual_stats_sets, rd_residual_dist_sets), in calls of at most MAX_SETS sets."""
+        n = cls.numel()
+        for k in range(0, len(sets), MAX_SETS):
+            need_a, thr_a, src_a = _set_arrays(sets[k:k + MAX_SETS])
+            self._queue(None if quantiles_only else "residual_stats_sets", "residual_dist_sets", n,
+                        (ptr(src0), ptr(src1), ptr(cls), n, src_a, need_a, thr_a, len(need_a)))
+
+    def pooled(self, res, n_planes, p0, p1, cls, valid, sets):
+        """sets: [(need bits, threshold or None)] over planes p0 .. p1 - 1 of `res` [P, rows, cols] -> len(sets) rows
+        (rd_residual_stats_pooled, rd_residual_dist_pooled)."""
+        n = cls.numel()
+        need_a, thr_a = _set_arrays(sets)
+        self._queue("residual_stats_pooled", "residual_dist_pooled", n,
+                    (ptr(res), n, n_planes, p0, p1, ptr(cls), ptr(valid), n, need_a, thr_a, len(sets)))
+
+    def host(self):
+        """The one read-back -> [n_rows, 8 + width]: a row carries its eight numbers and behind them its (count, quantiles,
+        shares)."""
+        h, n = self.buf.cpu().numpy(), self.n_rows
+        return np.concatenate((h[:n * 8].reshape(n, 8), h[n * 8:].reshape(n, self.width)), axis=1)
+
+
+def _fill(dist, st, row):
+    """The quantile part of a host row of _Rows into st, under the keys of the options given (none: nothing)."""
     if dist is not None:
-        dist.fill(st, dfull)
+        dist.fill(st, row[8:])
+
+
+def _truncated_dict(row, thr, dist):
+    """The 'truncated' sub-dict of the reference's get_statistics from the row of a truncated set."""
+    st = AttrDict(count_total=float(row[0]), threshold=thr, MAE=float(row[3]), RMSE=float(row[4]),
+                  absolute_median=float(row[5]), median=float(row[6]), NMAD=float(row[7]))
+    _fill(dist, st, row)
     return st
 
 
-def _class_stats(rows, classes, thr, dist=None, drows=None):
-    """rows [len(classes) * (2 if thr else 1), 8] in class order (full, truncated) -> {class: stats}; drows: the rows of the
-    quantile call over the same sets."""
-    step = 2 if thr else 1
-    if dist is None:
-        return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr))
-                        for q, c in enumerate(classes))
-    return AttrDict((c, _stats_dict(rows[q * step], rows[q * step + 1] if thr else None, thr, dist, drows[q * step],
-                                    drows[q * step + 1] if thr else None)) for q, c in enumerate(classes))
+def _stats_dict(full, trunc, thr, dist=None):
+    """host rows of _Rows (or rows of eight) -> the reference's get_statistics dict [with the abs_quantile / quantile / within keys
+    of the options given, in the truncated sub-dict too]."""
+    st = AttrDict(truncation=bool(thr))
+    if thr:
+        st.truncated = _truncated_dict(trunc, thr, dist)
+    st.update(zip(_KEYS, (float(v) for v in full)))        # the zip ends with the eight names
+    _fill(dist, st, full)
+    return st
+
+
+def _class_stats(rows, classes, thr, dist=None):
+    """host rows [len(classes) * (2 if thr else 1), 8 + width] in class order (full, truncated) -> {class: stats}"""
+    return AttrDict((c, _stats_dict(*_full_and_truncated(rows, q, thr), thr, dist)) for q, c in enumerate(classes))
 
 
 def _float_raster(x, dev):
@@ -275,8 +308,10 @@ def _float_raster(x, dev):
 
 
 def _eval_inputs(rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev):
-    """What a classification pass needs besides the DSMs: the uint8 device masks (building already dilated), the classes
-    they define, the area rectangles as a ctypes array and the nodata value."""
+    """What a classification pass needs besides the DSMs -> (classes, masks, grid): the classes the masks define; the uint8
+    device masks gm, bdil (building, already dilated), bnod, water, forest, which the caller holds until its launch is queued;
+    and the area rectangles as a ctypes array, their number, the raster shape and the nodata value.  `*map(ptr, masks), *grid`
+    is the run of arguments rd_eval_classify and rd_eval_classify_planes take in the same order."""
     gm = None if mask_gt is None else _mask_pair(mask_gt, dev)[0]
     bdil = bnod = water = forest = None
     classes = ["all"]
@@ -296,7 +331,7 @@ def _eval_inputs(rows, cols, area_defn, mask_gt, mask_building, mask_water, mask
     rects = _rects(area_defn, rows, cols)
     rect_a = None if rects is None else (ctypes.c_int * (4 * max(len(rects), 1)))(*[v for r in rects for v in r])
     nd = float("nan") if nodata is None else float(nodata)
-    return gm, bdil, bnod, water, forest, classes, rect_a, (-1 if rects is None else len(rects)), nd
+    return classes, (gm, bdil, bnod, water, forest), (rect_a, -1 if rects is None else len(rects), rows, cols, nd)
 
 
 def _classified(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev, who):
@@ -309,16 +344,14 @@ def _classified(prediction, initial, gt, area_defn, mask_gt, mask_building, mask
         raise ValueError(f"{who}: prediction {tuple(pred.shape)}, initial {tuple(init.shape)} and ground truth "
                          f"{tuple(g.shape)} must be equal 2-D rasters")
     rows, cols = pred.shape
-    gm, bdil, bnod, water, forest, classes, rect_a, n_rects, nd = _eval_inputs(
-        rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev)
+    classes, masks, grid = _eval_inputs(rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev)
     r_before = torch.empty((rows, cols), dtype=torch.float64, device=dev)
     r_after = torch.empty_like(r_before)
     cls = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         check(load().rd_eval_classify(ptr(pred), ptr(init), int(init.dtype == torch.float64), ptr(g),
-                                      int(g.dtype == torch.float64), ptr(gm), ptr(bdil), ptr(bnod), ptr(water), ptr(forest),
-                                      rect_a, n_rects, rows, cols, nd, ptr(r_before), ptr(r_after), ptr(cls), stream_ptr()),
-              "eval_classify")
+                                      int(g.dtype == torch.float64), *map(ptr, masks), *grid, ptr(r_before), ptr(r_after),
+                                      ptr(cls), stream_ptr()), "eval_classify")
     return r_before, r_after, cls, classes
 
 
@@ -329,15 +362,12 @@ def _evaluate(prediction, initial, gt, area_defn, mask_gt, mask_building, mask_w
                                                   mask_forest, nodata, dev, "evaluate")
     thr = residual_threshold
     sets = [(src, valid | CLASS_BITS[c], t) for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)) for c in classes
-            for t in ((None, thr) if thr else (None,))]
+            for t in _variants(thr)]
+    rows = _Rows(len(sets), dist, dev)
+    rows.sets(r_before, r_after, cls, sets)
+    host = rows.host()
     half = len(sets) // 2                              # source-major: the initial DSM's rows, then the refined DSM's
-    if dist is None:
-        res = _run_sets(r_before, r_after, cls, sets, dev)
-        stats = AttrDict(before=_class_stats(res[:half], classes, thr), after=_class_stats(res[half:], classes, thr))
-    else:
-        res, dres = _run_sets(r_before, r_after, cls, sets, dev, dist)
-        stats = AttrDict(before=_class_stats(res[:half], classes, thr, dist, dres[:half]),
-                         after=_class_stats(res[half:], classes, thr, dist, dres[half:]))
+    stats = AttrDict(before=_class_stats(host[:half], classes, thr, dist), after=_class_stats(host[half:], classes, thr, dist))
     return stats, r_after, cls, classes
 
 
@@ -567,40 +597,15 @@ def get_statistics_masked(residuals_masked, residual_threshold=None, device="cud
     if r.numel() == 0:                                 # nothing to read: the statistics of an empty set
         r = torch.zeros(1, dtype=torch.float64, device=dev)
         valid = torch.zeros(1, dtype=torch.uint8, device=dev)
-    sets = [(0, 1, None)] + ([(0, 1, residual_threshold)] if residual_threshold else [])
-    if dist is None:
-        res = _run_sets(r, None, valid, sets, dev)
-        return _stats_dict(res[0], res[1] if residual_threshold else None, residual_threshold)
-    res, dres = _run_sets(r, None, valid, sets, dev, dist)
-    return _stats_dict(res[0], res[1] if residual_threshold else None, residual_threshold, dist, dres[0],
-                       dres[1] if residual_threshold else None)
+    sets = [(0, 1, t) for t in _variants(residual_threshold)]
+    rows = _Rows(len(sets), dist, dev)
+    rows.sets(r, None, valid, sets)
+    return _stats_dict(*_full_and_truncated(rows.host(), 0, residual_threshold), residual_threshold, dist)
 
 
 # ---- every pair plane of a sweep, and the pool of all pairs (test.py:191-357) ----------------------------------------------
 VALID_EXTRA = 64                                      # RD_CLS_VALID_EXTRA (include/resdepth_hip_eval.h)
 MAX_PLANES = 16                                       # RD_EVAL_MAX_PLANES
-
-
-def _queue_pooled(res, n_planes, p0, p1, cls, valid, sets, out, dev):
-    """rd_residual_stats_pooled of planes p0 .. p1 - 1 of `res` [P, rows, cols] into out [len(sets), 8] (device), enqueued
-    only.  sets: [(need bits, threshold or None)]."""
-    n, ns = cls.numel(), len(sets)
-    lib = load()
-    need_a, thr_a = _set_arrays(sets)
-    ws = workspace(lib.rd_residual_stats_pooled_ws_bytes(n, ns), dev, slot=3)
-    check(lib.rd_residual_stats_pooled(ptr(res), n, n_planes, p0, p1, ptr(cls), ptr(valid), n, need_a, thr_a, ns, ptr(out),
-                                       ws.data_ptr(), ws.numel(), stream_ptr()), "residual_stats_pooled")
-
-
-def _queue_dist_pooled(res, n_planes, p0, p1, cls, valid, sets, dist, out, dev):
-    """rd_residual_dist_pooled over the sets of _queue_pooled into out [len(sets), dist.width] (device), enqueued only."""
-    n, ns = cls.numel(), len(sets)
-    lib = load()
-    need_a, thr_a = _set_arrays(sets)
-    ws = workspace(lib.rd_residual_dist_pooled_ws_bytes(n, ns, dist.n_q, dist.n_t), dev, slot=4)
-    check(lib.rd_residual_dist_pooled(ptr(res), n, n_planes, p0, p1, ptr(cls), ptr(valid), n, need_a, thr_a, ns, dist.q_a,
-                                      dist.mode_a, dist.n_q, dist.tau_a, dist.n_t, ptr(out), ws.data_ptr(), ws.numel(),
-                                      stream_ptr()), "residual_dist_pooled")
 
 
 def _is_sweep(x):
@@ -639,8 +644,7 @@ def _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_
     if fused is not None and tuple(fused.shape) != tuple(init.shape):
         raise ValueError(f"evaluate: fused surface {tuple(fused.shape)} != raster shape {tuple(init.shape)}")
     rows, cols = init.shape
-    gm, bdil, bnod, water, forest, classes, rect_a, n_rects, nd = _eval_inputs(
-        rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev)
+    classes, masks, grid = _eval_inputs(rows, cols, area_defn, mask_gt, mask_building, mask_water, mask_forest, nodata, dev)
     # host planes are uploaded once into a buffer of this call and turned into residuals in place; a device tensor of the
     # caller is read where it is and the residuals go to a buffer of their own
     planes, own = _private_f64(pairs, dev)
@@ -653,46 +657,26 @@ def _evaluate_pairs(pairs, initial, gt, area_defn, mask_gt, mask_building, mask_
     cls = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
     valid = torch.empty((rows, cols), dtype=torch.int16, device=dev)
     thr = residual_threshold
-    lib = load()
     with torch.cuda.device(dev):
-        check(lib.rd_eval_classify_planes(ptr(planes), rows * cols, n_planes, ptr(fz), ptr(init),
-                                          int(init.dtype == torch.float64), ptr(g), int(g.dtype == torch.float64), ptr(gm),
-                                          ptr(bdil), ptr(bnod), ptr(water), ptr(forest), rect_a, n_rects, rows, cols, nd,
-                                          ptr(r_before), ptr(res), ptr(r_fused), ptr(cls), ptr(valid), stream_ptr()),
-              "eval_classify_planes")
-        psets = [(CLASS_BITS[c], t) for c in classes for t in ((None, thr) if thr else (None,))]
-        # one device buffer for the eight numbers and, with options, the quantile rows behind them: one read-back
-        n_rows = (n_planes + 1) * len(psets)
-        buf = torch.empty(n_rows * (8 + (dist.width if dist else 0)), dtype=torch.float64, device=dev)
-        out = buf[:n_rows * 8].view(n_planes + 1, len(psets), 8)
-        dout = buf[n_rows * 8:].view(n_planes + 1, len(psets), dist.width) if dist else None
-        for p in range(n_planes + 1):                  # the pairs, then the pool of all of them
-            p0, p1 = (p, p + 1) if p < n_planes else (0, n_planes)
-            _queue_pooled(res, n_planes, p0, p1, cls, valid, psets, out[p], dev)
-            if dist is not None:
-                _queue_dist_pooled(res, n_planes, p0, p1, cls, valid, psets, dist, dout[p], dev)
-    # the initial DSM and the fused surface: two sources of the existing sets kernel, off the same class byte
+        check(load().rd_eval_classify_planes(ptr(planes), rows * cols, n_planes, ptr(fz), ptr(init),
+                                             int(init.dtype == torch.float64), ptr(g), int(g.dtype == torch.float64),
+                                             *map(ptr, masks), *grid, ptr(r_before), ptr(res), ptr(r_fused), ptr(cls),
+                                             ptr(valid), stream_ptr()), "eval_classify_planes")
+    psets = [(CLASS_BITS[c], t) for c in classes for t in _variants(thr)]
+    # the initial DSM and the fused surface: two sources of the sets kernel, off the same class byte
     sets = [(0, VALID_BEFORE | b, t) for b, t in psets]
     if fz is not None:
         sets += [(1, VALID_EXTRA | b, t) for b, t in psets]
-    k = len(psets)
-    if dist is None:
-        single = _run_sets(r_before, r_fused, cls, sets, dev)
-        rows_out = out.cpu().numpy()
-        stats = AttrDict(before=_class_stats(single[:k], classes, thr),
-                         pairs=[_class_stats(rows_out[p], classes, thr) for p in range(n_planes)],
-                         pooled=_class_stats(rows_out[n_planes], classes, thr))
-        if fz is not None:
-            stats.fused = _class_stats(single[k:], classes, thr)
-        return stats, classes
-    single, dsingle = _run_sets(r_before, r_fused, cls, sets, dev, dist)
-    host = buf.cpu().numpy()
-    rows_out, drows = host[:n_rows * 8].reshape(out.shape), host[n_rows * 8:].reshape(dout.shape)
-    stats = AttrDict(before=_class_stats(single[:k], classes, thr, dist, dsingle[:k]),
-                     pairs=[_class_stats(rows_out[p], classes, thr, dist, drows[p]) for p in range(n_planes)],
-                     pooled=_class_stats(rows_out[n_planes], classes, thr, dist, drows[n_planes]))
+    out = _Rows((n_planes + 1) * len(psets) + len(sets), dist, dev)      # one buffer for all of them: one read-back
+    for p in range(n_planes + 1):                      # the pairs, then the pool of all of them
+        p0, p1 = (p, p + 1) if p < n_planes else (0, n_planes)
+        out.pooled(res, n_planes, p0, p1, cls, valid, psets)
+    out.sets(r_before, r_fused, cls, sets)
+    host = out.host()
+    blocks = [_class_stats(host[k:k + len(psets)], classes, thr, dist) for k in range(0, len(host), len(psets))]
+    stats = AttrDict(before=blocks[n_planes + 1], pairs=blocks[:n_planes], pooled=blocks[n_planes])
     if fz is not None:
-        stats.fused = _class_stats(single[k:], classes, thr, dist, dsingle[k:])
+        stats.fused = blocks[n_planes + 2]
     return stats, classes
 
 
@@ -898,32 +882,19 @@ def evaluate_binned(prediction, initial, gt, by, edges, *, gsd=None, area_defn=N
     planes = torch.empty((groups, n), dtype=torch.uint8, device=dev)
     lib = load()
     edge_a = (ctypes.c_double * (n_bins + 1))(*cut)
-    per_bin = 4 if thr else 2                          # sets of a bin: initial, refined (each with its truncated set)
-    out = torch.empty((n_bins * per_bin, 8), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         check(lib.rd_bin_classes(ptr(cov), int(cov.dtype == torch.float64), ptr(cls), n, edge_a, n_bins, ptr(planes),
                                  stream_ptr()), "bin_classes")
-        ws = workspace(lib.rd_residual_stats_sets_ws_bytes(n, MAX_SETS), dev, slot=3)
-        for g in range(groups):
-            bins = range(g * BINS_PER_PLANE, min(n_bins, (g + 1) * BINS_PER_PLANE))
-            sets = [(src, valid | (4 << (b - g * BINS_PER_PLANE)), t) for b in bins
-                    for src, valid in ((0, VALID_BEFORE), (1, VALID_AFTER)) for t in ((None, thr) if thr else (None,))]
-            row0 = bins[0] * per_bin
-            for k in range(0, len(sets), MAX_SETS):     # a call takes 20 sets
-                part = sets[k:k + MAX_SETS]
-                need_a, thr_a, src_a = _set_arrays(part)
-                check(lib.rd_residual_stats_sets(ptr(r_before), ptr(r_after), ptr(planes[g]), n, src_a, need_a, thr_a, len(part),
-                                                 ptr(out[row0 + k:row0 + k + len(part)]), ws.data_ptr(), ws.numel(),
-                                                 stream_ptr()), "residual_stats_sets")
-    rows = out.cpu().numpy()
-    step = 2 if thr else 1
-    res = []
-    for b in range(n_bins):
-        q = rows[b * per_bin:(b + 1) * per_bin]
-        res.append(AttrDict(lo=e[b], hi=e[b + 1],
-                            initial=_stats_dict(q[0], q[1] if thr else None, thr),
-                            refined=_stats_dict(q[step], q[step + 1] if thr else None, thr)))
-    return res
+    # the sets of a bin: initial, refined (each with its truncated set), so two _variants steps of rows per bin
+    sides = ((0, VALID_BEFORE), (1, VALID_AFTER))
+    rows = _Rows(n_bins * len(sides) * len(_variants(thr)), None, dev)
+    for g in range(groups):
+        bins = range(g * BINS_PER_PLANE, min(n_bins, (g + 1) * BINS_PER_PLANE))
+        rows.sets(r_before, r_after, planes[g], [(src, valid | (4 << (b - g * BINS_PER_PLANE)), t) for b in bins
+                                                 for src, valid in sides for t in _variants(thr)])
+    host = rows.host()
+    return [AttrDict(lo=e[b], hi=e[b + 1], initial=_stats_dict(*_full_and_truncated(host, 2 * b, thr), thr),
+                     refined=_stats_dict(*_full_and_truncated(host, 2 * b + 1, thr), thr)) for b in range(n_bins)]
 
 
 def print_binned(stats, logger, unit=""):

@@ -22,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from resdepth_amd import _lib  # noqa: E402
-from resdepth_amd.evaluation import (CLASS_BITS, VALID_AFTER, _evaluate, _queue_pooled, evaluate_pairs_statistics,  # noqa: E402
+from resdepth_amd.evaluation import (CLASS_BITS, VALID_AFTER, _evaluate, _Rows, evaluate_pairs_statistics,  # noqa: E402
                                      get_statistics_masked)
 
 NODATA, THR = -9999.0, 2.5
@@ -107,8 +107,7 @@ def main():
         # the pooled passes with one set: same bytes, 3 selectors instead of 30
         res = pairs - gt.double()
         cls = torch.full((n, n), 8 | 16 | 32, dtype=torch.uint8, device=dev)
-        out1 = torch.empty((1, 8), dtype=torch.float64, device=dev)
-        prof1 = profile(lambda: _queue_pooled(res, n_planes, 0, n_planes, cls, None, [(0, None)], out1, dev))
+        prof1 = profile(lambda: _Rows(1, None, dev).pooled(res, n_planes, 0, n_planes, cls, None, [(0, None)]))
         del res, cls
 
         pairs_h, init_h, gt_h = pairs.cpu().numpy(), init.cpu().numpy(), gt.cpu().numpy()

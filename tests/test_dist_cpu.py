@@ -200,3 +200,34 @@ def test_the_options_are_checked_on_the_host():
                 dict(quantiles=(float("nan"),)), dict(abs_quantiles=[0.5] * 5, quantiles=[0.5] * 4), dict(within=[1.0] * 9)):
         with pytest.raises(ValueError):
             E._dist_options(bad.get("abs_quantiles"), bad.get("quantiles"), bad.get("within"))
+
+
+def test_host_rows_land_under_the_right_class_and_key():
+    """_class_stats on a synthetic read-back: three classes under a threshold, so six rows in (full, truncated) steps, each
+    row its eight numbers and behind them (count, one |residual| level, one signed level, two shares).  Every number is
+    distinct -- 100 * row + column -- so a value under a wrong class, in the wrong one of stats / stats.truncated or under a
+    wrong key shows."""
+    from resdepth_amd import evaluation as E
+    keys = ["count_total", "diff_max", "diff_min", "MAE", "RMSE", "absolute_median", "median", "NMAD"]
+    classes, thr = ["all", "building", "terrain"], 2.0
+    dist = E._dist_options((0.9,), (0.05,), (1.0, 2.0))
+    assert dist.width == 5
+    host = 100.0 * np.arange(6.0)[:, None] + np.arange(13.0)[None, :]
+    st = E._class_stats(host, classes, thr, dist)
+    assert list(st) == classes
+    for q, c in enumerate(classes):
+        full, trunc = 100.0 * (2 * q), 100.0 * (2 * q + 1)
+        extra = lambda base: {"abs_quantile": {0.9: base + 9}, "quantile": {0.05: base + 10},         # noqa: E731
+                              "within": {1.0: base + 11, 2.0: base + 12}}
+        want = {"truncation": True,
+                "truncated": {"count_total": trunc, "threshold": thr, "MAE": trunc + 3, "RMSE": trunc + 4,
+                              "absolute_median": trunc + 5, "median": trunc + 6, "NMAD": trunc + 7, **extra(trunc)},
+                **{k: full + j for j, k in enumerate(keys)}, **extra(full)}
+        assert st[c] == want, c
+        assert list(st[c]) == list(want) and list(st[c].truncated) == list(want["truncated"]), c     # the order of the keys too
+        assert all(type(v) is float for v in st[c].values() if not isinstance(v, (dict, bool))), c
+    # the same rows without options and without a threshold: one row per class, exactly the old keys
+    plain = E._class_stats(host, classes, None)
+    for q, c in enumerate(classes):
+        assert list(plain[c]) == ["truncation"] + keys, c
+        assert plain[c] == {"truncation": False, **{k: 100.0 * q + j for j, k in enumerate(keys)}}, c

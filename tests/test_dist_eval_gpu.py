@@ -122,6 +122,75 @@ def test_no_options_make_exactly_the_old_library_calls(case, monkeypatch):
     assert calls == old + ["rd_residual_dist_sets_ws_bytes", "rd_residual_dist_sets"]         # one more call, the same sets
 
 
+def _pairs_call(E, d, **opts):
+    p, pairs = _planes_case(31, H, W, 3)
+    return E.evaluate_pairs_statistics(pairs, *_args(p), fused=pairs[0], nodata=NODATA, **opts)
+
+
+def _binned_call(E, d, **opts):
+    """the 61 x 83 case of test_errmap_gpu.test_binned_statistics_match_the_restatement: eight bins under a threshold"""
+    from test_errmap_gpu import _dsms
+    rng = np.random.RandomState(21)
+    pred, init, gt = _dsms(rng, (61, 83))
+    by = rng.rand(61, 83).astype(np.float32) * 10.0
+    by[rng.rand(61, 83) < 0.05] = np.nan
+    edges = [0.0, 1.0, 2.5, 4.0, 4.5, 6.0, 7.0, 9.0, 10.0]
+    return E.evaluate_binned(pred, init, gt, by, edges, nodata=NODATA, residual_threshold=8.0)
+
+
+OPTS = dict(abs_quantiles=(0.68, 0.90, 0.95), within=WITHIN)
+POOLED = [(0, 1), (1, 2), (2, 3), (0, 3)]                         # planes p0 .. p1 - 1 of a call: the three pairs, then their pool
+# every launching entry point a call makes, in order; a call that takes sets with their number (and the planes it draws from):
+# five classes x (full, truncated) = 10 sets a pair or pool, 20 for the initial DSM and the fused surface
+CALLS = {
+    "pairs": (_pairs_call, {}, ["rd_dilate_mask", "rd_eval_classify_planes"]
+              + [("rd_residual_stats_pooled", p0, p1, 10) for p0, p1 in POOLED] + [("rd_residual_stats_sets", 20)]),
+    "pairs_options": (_pairs_call, OPTS, ["rd_dilate_mask", "rd_eval_classify_planes"]
+                      + [(name, p0, p1, 10) for p0, p1 in POOLED for name in ("rd_residual_stats_pooled", "rd_residual_dist_pooled")]
+                      + [("rd_residual_stats_sets", 20), ("rd_residual_dist_sets", 20)]),
+    "masked": (lambda E, d, **o: E.get_statistics_masked(d["pred"] - d["gt"], THR, **o), {}, [("rd_residual_stats_sets", 2)]),
+    "masked_options": (lambda E, d, **o: E.get_statistics_masked(d["pred"] - d["gt"], THR, **o), OPTS,
+                       [("rd_residual_stats_sets", 2), ("rd_residual_dist_sets", 2)]),
+    "get_statistics": (lambda E, d, **o: E.get_statistics(d["pred"], d["gt"], NODATA, None, THR, **o), dict(within=WITHIN),
+                       ["rd_residual_stats", "rd_residual_stats", ("rd_residual_dist_sets", 2)]),
+    "error_map": (lambda E, d, **o: E.error_map(d["pred"], d["gt"], 16, initial=d["init"], mask_gt=d["gt_mask"],
+                                                mask_building=d["building"], nodata=NODATA), {},
+                  ["rd_dilate_mask", "rd_eval_classify", "rd_cell_stats", "rd_cell_stats"]),
+    # 8 bins x (initial, refined) x (full, truncated): 24 sets on the first plane of six bins -- a call of 20 and one of 4 --
+    # and 8 on the second
+    "binned": (_binned_call, {}, ["rd_eval_classify", "rd_bin_classes", ("rd_residual_stats_sets", 20),
+                                  ("rd_residual_stats_sets", 4), ("rd_residual_stats_sets", 8)]),
+}
+
+
+@pytest.mark.parametrize("path", list(CALLS))
+def test_every_path_makes_exactly_its_library_calls(case, monkeypatch, path):
+    """the spy of the test above on every other path of the front end, recording at the call"""
+    from resdepth_amd import _lib, evaluation as E
+    run, opts, want = CALLS[path]
+    calls = []
+    real = _lib.load()
+
+    class Spy:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if not name.startswith("rd_") or name.endswith("_ws_bytes"):
+                return fn
+
+            def recorded(*a):
+                if name in ("rd_residual_stats_sets", "rd_residual_dist_sets"):
+                    calls.append((name, a[7]))                    # (src0, src1, cls, n, set_src, set_need, set_thr, n_sets, ...
+                elif name in ("rd_residual_stats_pooled", "rd_residual_dist_pooled"):
+                    calls.append((name, a[3], a[4], a[10]))       # (src, stride, n_planes, p0, p1, cls, valid, n, need, thr, n_sets
+                else:
+                    calls.append(name)
+                return fn(*a)
+            return recorded
+    monkeypatch.setattr(E, "load", lambda: Spy())
+    run(E, case[0], **opts)
+    assert calls == want
+
+
 def test_evaluate_pairs_statistics_per_pair_pool_and_fused():
     from resdepth_amd import evaluation as E
     d, pairs = _planes_case(31, H, W, 3)

@@ -62,7 +62,7 @@ size_t rd_masked_loss_ws_bytes(int n, int h, int w);
 
 /* sums[0..7] (fp64, device) = A, C, D, S, Q, 0, 0, 0 of the batch (all eight are written: a data-parallel caller all-reduces
  * the whole array).  yp, y: [n][h][w] fp32; mask: [n][h][w] uint8 (torch.bool); mean, std: [n] fp32.  One pass over yp, y and
- * mask (9 bytes per pixel), two launches: masked_loss_partial_kernel<vector?> and masked_loss_reduce_kernel.  A scratch smaller
+ * mask (9 bytes per pixel), two launches: masked_loss_partial_kernel<vector?, false> and masked_loss_reduce_kernel<5>.  A scratch smaller
  * than rd_masked_loss_ws_bytes(n, h, w) is refused (RD_ERR_WS) with nothing launched.  delta > 0 is required for
  * RD_LOSS_HUBER only. */
 int rd_masked_loss_partial(const float* yp, const float* y, const uint8_t* mask, const float* mean, const float* std,
@@ -72,7 +72,7 @@ int rd_masked_loss_partial(const float* yp, const float* y, const uint8_t* mask,
 /* From sums (after any all-reduce): loss[0] and mae[0] (fp32, one rounding of the fp64 value) and dyp [n][h][w], each
  * nullable.  gout_dev: the upstream gradient as a DEVICE scalar (NULL = 1).  numel_total is the global element count; the
  * data term divides by C directly, so it does not enter the result (it is accepted so that the call mirrors
- * rd_masked_l1_finish and a caller may check it: it must be > 0).  One launch: masked_loss_finish_kernel<vector?, slope?>;
+ * rd_masked_l1_finish and a caller may check it: it must be > 0).  One launch: masked_loss_finish_kernel<vector?, slope?, false>;
  * with lambda == 0 no halo is staged and the kernel streams 13 bytes per pixel; with dyp == NULL one block runs.
  * Nothing outside loss[0], mae[0] and the n * h * w floats of dyp is written. */
 int rd_masked_loss_finish(const float* yp, const float* y, const uint8_t* mask, const float* mean, const float* std,

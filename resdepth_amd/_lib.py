@@ -212,6 +212,16 @@ SIGNATURES_TAIL = {
     "rd_bn_act_pool_fwd_tailskip": (I, [P, P, P, P, P, F, P, P, P, P, P, P, I, I, I, I, P]),
     "rd_conv3x3_last_fwd_tail_pre": (I, [P, P, P, P, P, I, P, I, I, I, P]),
 }
+# include/resdepth_hip_wloss.h (per-pixel weights for the masked losses, weight tiles of a training batch), one to one as above
+SIGNATURES_WLOSS = {
+    "rd_weighted_loss_ws_bytes": (SZ, [I, I, I]),
+    "rd_weighted_loss_partial": (I, [P, P, P, P, P, P, P, I, I, I, I, D, D, P, SZ, P]),
+    "rd_weighted_loss_finish": (I, [P, P, P, P, P, P, P, D, I, D, D, D, P, P, P, P, I, I, I, P]),
+    "rd_assemble_train_weights": (I, [P, I, P, I, I, I, P, P]),
+}
+# the constants of that header
+WEIGHT_KINDS = {"f32": 0, "class_u8": 1}
+WEIGHT_TABLE = 256
 
 
 class ProfEntry(C.Structure):
@@ -234,7 +244,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
                 + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()) \
-                + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()) + list(SIGNATURES_TAIL.items()):
+                + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()) + list(SIGNATURES_TAIL.items()) \
+                + list(SIGNATURES_WLOSS.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -339,6 +339,66 @@ __global__ __launch_bounds__(256) void train_patch_write(const rd_train_raster* 
     }
 }
 
+// ---- weight tiles (include/resdepth_hip_wloss.h) ---------------------------------------------------------------------------
+// grid (sample, row block): a lane writes four adjacent output pixels (one 16-byte store) and gathers their sources through
+// aug_src, the way train_patch_write orients the target plane; a row that is neither rotated nor mirrored left-right is one
+// 16-byte load (fp32 weights) or one 4-byte load (class bytes, looked up in the raster's table)
+__global__ __launch_bounds__(256) void train_weight_write(const rd_weight_raster* __restrict__ rasters, int n_rasters,
+                                                          const int* __restrict__ samples, int n, int T, int rows_per_block,
+                                                          float* __restrict__ out) {
+    const int i = blockIdx.x, rb = blockIdx.y, t = threadIdx.x;
+    const int id = samples[i], y0 = samples[n + i], x0 = samples[2 * n + i], a = samples[3 * n + i];
+    const float qnan = __int_as_float(0x7fc00000);
+    bool ok = id >= 0 && id < n_rasters;
+    const rd_weight_raster& R = rasters[ok ? id : 0];
+    const bool cls = R.kind == RD_WEIGHT_CLASS_U8;
+    ok = ok && (R.kind == RD_WEIGHT_F32 || cls) && R.plane != nullptr && (!cls || R.table != nullptr) && y0 >= 0 && x0 >= 0 &&
+         y0 + T <= R.height && x0 + T <= R.width;
+    const int W = R.width;
+    const float* srcf = nullptr;
+    const uint8_t* srcb = nullptr;
+    const float* __restrict__ tab = R.table;
+    bool vec = false;
+    if (ok) {
+        const bool plain_rows = (a & 11) == 0 && (W & 3) == 0;      // k == 0 (bits 0-1) and no left-right mirror (bit 3)
+        if (cls) {
+            srcb = static_cast<const uint8_t*>(R.plane) + (long)y0 * W + x0;
+            vec = plain_rows && ((uintptr_t)srcb & 3) == 0;
+        } else {
+            srcf = static_cast<const float*>(R.plane) + (long)y0 * W + x0;
+            vec = plain_rows && ((uintptr_t)srcf & 15) == 0;
+        }
+    }
+    float* dst = out + (long)i * T * T;
+    const int TQ = T / 4, r0 = rb * rows_per_block, r1 = min(T, r0 + rows_per_block);
+    for (int e = t; e < (r1 - r0) * TQ; e += 256) {
+        const int r = r0 + e / TQ, c = (e % TQ) * 4;
+        float4 v = make_float4(qnan, qnan, qnan, qnan);
+        if (ok) {
+            if (vec) {       // the source row is r or its up-down mirror, columns as they are
+                const long o = (long)((a & 4) ? T - 1 - r : r) * W + c;
+                if (cls) {
+                    const uchar4 b = *reinterpret_cast<const uchar4*>(srcb + o);
+                    v = make_float4(tab[b.x], tab[b.y], tab[b.z], tab[b.w]);
+                } else {
+                    v = *reinterpret_cast<const float4*>(srcf + o);
+                }
+            } else {
+                float xs[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int sr, sc;
+                    aug_src(a, T, r, c + j, sr, sc);
+                    const long o = (long)sr * W + sc;
+                    xs[j] = cls ? tab[srcb[o]] : srcf[o];
+                }
+                v = make_float4(xs[0], xs[1], xs[2], xs[3]);
+            }
+        }
+        *reinterpret_cast<float4*>(dst + (long)r * T + c) = v;
+    }
+}
+
 static bool region_plan(RegionPlan* rp, int height, int width, long long plane_stride, const int* plane_idx, int n_planes,
                         int n_stack, const int* rects, int n_rects) {
     if (n_planes <= 0 || n_planes > RD_REGION_MAX_PLANES || n_rects <= 0 || n_rects > RD_REGION_MAX_RECTS) return false;
@@ -454,6 +514,20 @@ int rd_assemble_train_patches(const rd_train_raster* rasters, int n_rasters, con
     RD_LAUNCH(train_patch_write, dim3(n, planes_out, cdiv(tile, rows_per_block)), dim3(256), 0, (hipStream_t)s, rasters, n_rasters,
               samples, n, views, dsm_channel, tile, (const double*)sums, rows_per_block, input, target, mask, dsm_mean_out);
     RD_LAUNCH_CHECK("train_patch_write");
+    return RD_OK;
+}
+
+int rd_assemble_train_weights(const rd_weight_raster* rasters, int n_rasters, const int* samples, int n, int views, int tile,
+                              float* out, rd_stream_t s) {
+    RD_REQUIRE(rasters && n_rasters > 0 && samples && out && n > 0 && views >= 0, "rd_assemble_train_weights: bad arguments");
+    RD_REQUIRE(tile >= 4 && tile % 4 == 0 && tile <= 1024,
+               "rd_assemble_train_weights: tile must be a multiple of 4 in 4..1024 (got %d)", tile);
+    RD_REQUIRE((uintptr_t)out % 16 == 0, "rd_assemble_train_weights: out must be 16-byte aligned");
+    const int rows_per_block = tile_rows_per_block(tile);
+    ProfScope ps((hipStream_t)s, "train_weight_write", 0, 8.0 * (double)n * tile * tile);
+    RD_LAUNCH(train_weight_write, dim3(n, cdiv(tile, rows_per_block)), dim3(256), 0, (hipStream_t)s, rasters, n_rasters, samples,
+              n, tile, rows_per_block, out);
+    RD_LAUNCH_CHECK("train_weight_write");
     return RD_OK;
 }
 

@@ -55,13 +55,13 @@ class GraphedTrainStep:
         self._ws_held = None                     # the side stream's scratch buffers the captured kernels point into
 
     # ---- the eager iteration (lib/Trainer.py:212-222) -------------------------------------------------------------------
-    def _eager(self, x, y, mask, mean, std):
+    def _eager(self, x, y, mask, mean, std, weight=None):
         # gradients a previous call left in place (keep_grads, or a replay's graph-owned buffers) must not be ACCUMULATED into:
         # every iteration starts from "no gradient", like lib/Trainer.py:221-222; keep_grads only decides what is left afterwards
         for p in self.params:
             p.grad = None
         out = self.model(x)
-        loss = self._criterion(out, y, mask, mean, std)
+        loss = self._criterion(out, y, mask, mean, std, weight)
         loss.backward()
         self.optimizer.step()
         if not self.keep_grads:
@@ -69,14 +69,17 @@ class GraphedTrainStep:
                 p.grad = None
         return loss.detach()
 
-    def _criterion(self, out, y, mask, mean, std):
-        """The iteration's loss; leaves the masked MAE of a MaskedLoss in `mae`."""
+    def _criterion(self, out, y, mask, mean, std, weight=None):
+        """The iteration's loss; leaves the masked MAE of a MaskedLoss (or of any loss that takes a weight) in `mae`."""
         gs = getattr(self.model, "grad_sync", None)
         if self.loss is None:
-            return masked_l1_loss(out, y, mask, mean, std, grad_sync=gs)
+            if weight is None:
+                return masked_l1_loss(out, y, mask, mean, std, grad_sync=gs)
+            loss, self.mae = masked_loss(out, y, mask, mean, std, "l1", grad_sync=gs, return_mae=True, weight=weight)
+            return loss
         m = self.loss
         loss, self.mae = masked_loss(out, y, mask, mean, std, m.kind, m.delta, m.slope_weight,
-                                     grad_sync=m.grad_sync if m.grad_sync is not None else gs, return_mae=True)
+                                     grad_sync=m.grad_sync if m.grad_sync is not None else gs, return_mae=True, weight=weight)
         return loss
 
     # ---- hooks of the launch-plan variant (resdepth_amd/plan.py) -----------------------------------------------------------
@@ -91,7 +94,24 @@ class GraphedTrainStep:
         instead returns that iteration's loss (and has set `why_eager` and left `p.grad` as `keep_grads` asks)."""
         self._graph.replay()
 
-    def _eligible(self, x):
+    @staticmethod
+    def _weight_reason(weight):
+        """Why a loss weight keeps the iteration eager (None: it does not).  masked_loss would convert such a weight with torch
+        kernels INSIDE the iteration; a launch plan does not hold them (the hazard ADVICE.md names for the mask)."""
+        if weight is None:
+            return None
+        if not isinstance(weight, torch.Tensor) or not weight.is_cuda:
+            return "loss weight not on the HIP device"
+        if weight.dtype != torch.float32:
+            return f"loss weight is {weight.dtype}, not float32: its conversion is a torch kernel inside the iteration"
+        if not weight.is_contiguous():
+            return "loss weight is not contiguous: its copy is a torch kernel inside the iteration"
+        return None
+
+    def _eligible(self, x, weight=None):
+        why = self._weight_reason(weight)
+        if why is not None:
+            return why
         if not x.is_cuda:
             return "batch not on a HIP device"
         if not self.model.training:
@@ -145,14 +165,14 @@ class GraphedTrainStep:
             self._record_begin()
             try:
                 out = self.model(static[0])
-                loss = self._criterion(out, static[1], static[2], static[3], static[4])
+                loss = self._criterion(out, *static[1:])
                 loss.backward(self._one)
                 self.optimizer.capture_step()
                 sloss = loss.detach()
             finally:
                 self._record_end()
         self._graph, self._static, self._loss = g, static, sloss
-        self._mae = self.mae if self.loss is not None else None
+        self._mae = self.mae if (self.loss is not None or len(batch) > 5) else None
         self._grads = [p.grad for p in self.params]
         self._key = self._shape_key(batch)
         self._cap_token = self.optimizer._cap
@@ -161,12 +181,14 @@ class GraphedTrainStep:
         side = getattr(self.model, "_side_stream", None)
         self._ws_held = _lib.workspaces_of(side) if side is not None else []
 
-    def __call__(self, x, y, mask, mean, std):
+    def __call__(self, x, y, mask, mean, std, weight=None):
         """-> the iteration's loss as a 0-dim device tensor.  After a replay it is the graph's own output buffer: read it (or
-        add it into an accumulator on the same stream) before the next call."""
+        add it into an accumulator on the same stream) before the next call.  weight: optional per-pixel loss weights
+        ([N,1,H,W] fp32, contiguous, on the device), a sixth static buffer; whether a weight is there is part of what a capture
+        is valid for."""
         self._calls += 1
-        batch = (x, y, mask, mean, std)
-        why = self._eligible(x)
+        batch = (x, y, mask, mean, std) if weight is None else (x, y, mask, mean, std, weight)
+        why = self._eligible(x, weight)
         if why is None and not all(isinstance(t, torch.Tensor) and t.is_cuda for t in batch):
             why = "target / mask / mean / std not on the HIP device"
         if why is None and self._calls <= self.warmup:
@@ -177,6 +199,9 @@ class GraphedTrainStep:
             key = self._shape_key(batch)
             if key[1] != self._key[1]:
                 self.invalidate()                # parameters re-homed since the capture: capture again (below)
+            elif len(key[0]) != len(self._key[0]):
+                why = "the captured iteration has a loss weight and this batch has none" if weight is None else \
+                    "the captured iteration has no loss weight"
             elif key[0] != self._key[0]:
                 why = "batch shape differs from the captured one"
         if why is not None:

@@ -10,7 +10,8 @@ all-reduced between the reduction and the finishing kernel.
 
 `masked_loss` / `MaskedLoss` are the same chain for the other criteria the reference's generic expression takes -- nn.MSELoss,
 nn.HuberLoss, nn.SmoothL1Loss -- plus an optional slope-consistency term on the residual's first differences, with the masked
-MAE reported beside the loss (include/resdepth_hip_loss.h).
+MAE reported beside the loss (include/resdepth_hip_loss.h).  Both take an optional per-pixel weight plane
+(include/resdepth_hip_wloss.h).
 """
 from __future__ import annotations
 
@@ -140,15 +141,74 @@ class _MaskedLoss(torch.autograd.Function):
         return (dyp,) + (None,) * 9
 
 
-def masked_loss(y_pred, y, loss_mask, mean, std, kind="l1", delta=1.0, slope_weight=0.0, grad_sync=None, return_mae=False):
+class _WeightedLoss(torch.autograd.Function):
+    """_MaskedLoss with a per-pixel weight plane (include/resdepth_hip_wloss.h): the same eight sums go through the all-reduce."""
+
+    @staticmethod
+    def forward(ctx, y_pred, y, mask_u8, weight, mean, std, grad_sync, kind, delta, scale, slope_weight):
+        with _lib.device_of(y_pred):
+            sums = ops.weighted_loss_partial(y_pred, y, mask_u8, weight, mean, std, kind, delta, scale)
+            numel = y_pred.numel()
+            if grad_sync is not None:
+                numel = grad_sync.allreduce_loss_sums(sums, numel)
+            loss, mae, _ = ops.weighted_loss_finish(y_pred, y, mask_u8, weight, mean, std, sums, numel, kind, delta, scale,
+                                                    slope_weight, want_grad=False)
+        ctx.save_for_backward(y_pred, y, mask_u8, weight, mean, std, sums)
+        ctx.spec = (numel, kind, delta, scale, slope_weight)
+        loss, mae = loss.reshape(()), mae.reshape(())
+        ctx.mark_non_differentiable(mae)
+        return loss, mae
+
+    @staticmethod
+    def backward(ctx, gout, _gmae):
+        y_pred, y, mask_u8, weight, mean, std, sums = ctx.saved_tensors
+        numel, kind, delta, scale, slope_weight = ctx.spec
+        g = gout.detach().to(torch.float32).contiguous()      # stays on the device: the kernel reads it through a pointer
+        with _lib.device_of(y_pred):
+            _, _, dyp = ops.weighted_loss_finish(y_pred, y, mask_u8, weight, mean, std, sums, numel, kind, delta, scale,
+                                                 slope_weight, gout=g, want_loss=False, want_mae=False)
+        return (dyp,) + (None,) * 10
+
+
+def _prep_weight(weight, y_pred):
+    """The weight plane as the kernels read it: fp32, contiguous, on y_pred's device, one value per pixel of [N,1,H,W]."""
+    if not isinstance(weight, torch.Tensor):
+        raise TypeError(f"weight: expected a tensor, got {type(weight).__name__}")
+    if not weight.is_cuda:
+        raise RuntimeError("resdepth_amd.masked_loss: weight must be on the HIP device (it is read by the loss kernels; no "
+                           "CPU fallback)")
+    if not (y_pred.dim() == 4 and y_pred.shape[1] == 1):
+        raise ValueError(f"y_pred of shape {tuple(y_pred.shape)}: a weight needs a 4-D [N,1,H,W] input")
+    n, _, h, w = y_pred.shape
+    if tuple(weight.shape) not in ((n, 1, h, w), (n, h, w)):
+        raise ValueError(f"weight of shape {tuple(weight.shape)}: expected {(n, 1, h, w)} or {(n, h, w)}")
+    if weight.device != y_pred.device:
+        raise RuntimeError(f"weight on {weight.device}, y_pred on {y_pred.device}")
+    return weight.detach().to(torch.float32).contiguous()
+
+
+def masked_loss(y_pred, y, loss_mask, mean, std, kind="l1", delta=1.0, slope_weight=0.0, grad_sync=None, return_mae=False,
+                weight=None):
     """loss = sum(m rho(r)) / sum(m) + slope_weight * sum|r_a - r_b| / #pairs over the valid horizontal and vertical neighbour
     pairs, r the de-normalised residual; rho by `kind`: "l1", "l2", "huber" (delta, in metres), "smooth_l1" (beta = delta).
     Returns the 0-dim device loss with autograd to y_pred; with return_mae also the masked MAE (0-dim, no gradient).
-    kind="l1" with slope_weight=0 IS masked_l1_loss (its kernels, its bits)."""
+    kind="l1" with slope_weight=0 IS masked_l1_loss (its kernels, its bits).
+
+    weight: optional per-pixel weights, [N,1,H,W] or [N,H,W] fp32 on the device, finite and >= 0 (not tested here):
+    loss = sum(m w rho(r)) / sum(m w) + slope_weight * sum(omega |r_a - r_b|) / sum(omega), omega the mean of a pair's two
+    weights.  The MAE stays the plain masked MAE.  weight=None is the unweighted path in every respect."""
     kind, delta, slope_weight = _check_spec(kind, delta, slope_weight)
     if slope_weight > 0.0 and not (y_pred.dim() == 4 and y_pred.shape[1] == 1):
         raise ValueError(f"y_pred of shape {tuple(y_pred.shape)}: slope_weight > 0 needs a 4-D [N,1,H,W] input (neighbour "
                          "pairs are taken inside one single-channel image)")
+    if weight is not None:
+        if not y_pred.is_cuda:
+            raise RuntimeError("resdepth_amd.masked_loss runs on a HIP device only (no CPU fallback)")
+        wt = _prep_weight(weight, y_pred)
+        yp, y, m, mean32, std32 = _prep(y_pred, y, loss_mask, mean, std)
+        code, delta, scale = _kernel_args(kind, delta)
+        loss, mae = _WeightedLoss.apply(yp, y, m, wt, mean32, std32, grad_sync, code, delta, scale, slope_weight)
+        return (loss, mae) if return_mae else loss
     if kind == "l1" and slope_weight == 0.0:
         loss = masked_l1_loss(y_pred, y, loss_mask, mean, std, grad_sync)
         return (loss, loss.detach()) if return_mae else loss
@@ -172,9 +232,9 @@ class MaskedLoss(torch.nn.Module):
     def extra_repr(self):
         return f"kind={self.kind!r}, delta={self.delta}, slope_weight={self.slope_weight}"
 
-    def forward(self, y_pred, y, loss_mask, mean, std):
+    def forward(self, y_pred, y, loss_mask, mean, std, weight=None):
         loss, self.last_mae = masked_loss(y_pred, y, loss_mask, mean, std, self.kind, self.delta, self.slope_weight,
-                                          self.grad_sync, return_mae=True)
+                                          self.grad_sync, return_mae=True, weight=weight)
         return loss
 
 

@@ -777,6 +777,42 @@ def masked_loss_finish(yp, y, mask, mean, std, sums, numel_total, kind=_lib.LOSS
     return loss, mae, dyp
 
 
+def weighted_loss_partial(yp, y, mask, weight, mean, std, kind=_lib.LOSS_KINDS["l2"], delta=1.0, scale=1.0):
+    """-> sums [8] float64 on device: A = sum |r| (unweighted), C = #valid, D = sum w rho(r), S = sum omega |r_a - r_b| over the
+    valid neighbour pairs, Q = sum omega, Wc = sum w over the valid pixels, then zeros (include/resdepth_hip_wloss.h)."""
+    n, h, w = _loss_geometry(yp)
+    sums = torch.empty(8, device=yp.device, dtype=torch.float64)
+    nb = load().rd_weighted_loss_ws_bytes(n, h, w)
+    ws = workspace(nb, yp.device)
+    check(load().rd_weighted_loss_partial(ptr(yp), ptr(y), ptr(mask), ptr(weight), ptr(mean), ptr(std), ptr(sums), n, h, w,
+                                          int(kind), float(delta), float(scale), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "weighted_loss_partial")
+    return sums
+
+
+def weighted_loss_finish(yp, y, mask, weight, mean, std, sums, numel_total, kind=_lib.LOSS_KINDS["l2"], delta=1.0, scale=1.0,
+                         slope_weight=0.0, gout=None, want_loss=True, want_mae=True, want_grad=True):
+    """-> (loss [1] | None, mae [1] | None, dyp | None), as masked_loss_finish."""
+    n, h, w = _loss_geometry(yp)
+    loss = torch.empty(1, device=yp.device, dtype=torch.float32) if want_loss else None
+    mae = torch.empty(1, device=yp.device, dtype=torch.float32) if want_mae else None
+    dyp = torch.empty_like(yp) if want_grad else None
+    check(load().rd_weighted_loss_finish(ptr(yp), ptr(y), ptr(mask), ptr(weight), ptr(mean), ptr(std), ptr(sums),
+                                         float(numel_total), int(kind), float(delta), float(scale), float(slope_weight),
+                                         ptr(gout), ptr(loss), ptr(mae), ptr(dyp), n, h, w, stream_ptr()), "weighted_loss_finish")
+    return loss, mae, dyp
+
+
+def assemble_train_weights(wdesc, n_rasters, tab, views, tile):
+    """-> [n, 1, tile, tile] fp32: the weight tiles of the samples of the device table `tab` (int32 [rows, n], the table of
+    rd_assemble_train_patches) from the rd_weight_raster table `wdesc` (uint8 device tensor), on the current stream."""
+    n = tab.shape[1]
+    out = torch.empty(n, 1, tile, tile, dtype=torch.float32, device=tab.device)
+    check(load().rd_assemble_train_weights(ptr(wdesc), int(n_rasters), ptr(tab), n, int(views), int(tile), ptr(out),
+                                           stream_ptr()), "assemble_train_weights")
+    return out
+
+
 def adam_step(p, g, m, v, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, grad_scale=1.0):
     check(load().rd_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), beta1, beta2, eps, weight_decay, step_size,
                               bc2_sqrt, grad_scale, stream_ptr()), "adam_step")

@@ -62,8 +62,11 @@ class PlannedTrainStep(GraphedTrainStep):
         self.n_launches = self.n_segments = 0
 
     # ---- eligibility: data parallelism is fine (host actions); what runs torch ops inside the iteration is not ----------------
-    def _eligible(self, x):
+    def _eligible(self, x, weight=None):
         m = self.model
+        why = self._weight_reason(weight)
+        if why is not None:
+            return why
         if not x.is_cuda:
             return "batch not on a HIP device"
         if not m.training:
@@ -216,7 +219,7 @@ class PlannedTrainStep(GraphedTrainStep):
             p.grad = None
         self.model.invalidate_packed()
         out = self.model(self._static[0])
-        loss = self._criterion(out, self._static[1], self._static[2], self._static[3], self._static[4])
+        loss = self._criterion(out, *self._static[1:])
         loss.backward()
         self.optimizer.capture_step()
         torch.cuda.synchronize()
@@ -246,14 +249,14 @@ class PlannedTrainStep(GraphedTrainStep):
             self._mae.copy_(want[n_state + 1])
         self._verified = True
 
-    def __call__(self, x, y, mask, mean, std):
-        x, y, mask, mean, std = self._canonical((x, y, mask, mean, std))
+    def __call__(self, x, y, mask, mean, std, weight=None):
+        x, y, mask, mean, std = self._canonical((x, y, mask, mean, std))       # the weight is never converted: see _eligible
         try:
-            out = super().__call__(x, y, mask, mean, std)
+            out = super().__call__(x, y, mask, mean, std, weight)
         except _PlanUnavailable as e:
             self.why_eager = f"plan unavailable: {e}"
             self.plan_rejected = str(e)
-            return self._eager(x, y, mask, mean, std)
+            return self._eager(x, y, mask, mean, std, weight)
         if getattr(self, "plan_rejected", None) and self.why_eager is None:
             self.why_eager = self.plan_rejected
         return out

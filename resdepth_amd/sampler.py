@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import tiling
+from . import _lib, ops, tiling
 from ._lib import check, load, ptr, stream_ptr
 
 # the per-tile metadata columns of a batch dict, in the column order of the loaders' tables ([pos (y, x) | box])
@@ -88,9 +88,15 @@ def _hand_over(device, item):
 
 class GpuPatchSampler:
     def __init__(self, dsm_input, dsm_target=None, orthos=None, tile_size: int = 256, nodata: float = -9999.0,
-                 dsm_std: float = 1.0, ortho_mean=None, ortho_std: float = 1.0, device="cuda"):
+                 dsm_std: float = 1.0, ortho_mean=None, ortho_std: float = 1.0, device="cuda", weight_raster=None,
+                 class_weights=None):
         """dsm_input / dsm_target: [H, W] float32; orthos: [V_total, H, W] float32 (planar).  ortho_mean=None => per-patch
-        mean over the views of the sample (lib/DsmOrthoDataset.py:231-233)."""
+        mean over the views of the sample (lib/DsmOrthoDataset.py:231-233).
+
+        weight_raster: per-pixel loss weights for the batches of GpuTrainSet / GpuValSet (`batch["loss_weight"]`), kept in HBM
+        beside the rasters: an [H, W] float32 raster of finite weights >= 0 (checked once, on the device), or -- with
+        class_weights, a table of at most 256 finite weights >= 0 (checked on the host) -- an [H, W] uint8 class raster whose
+        weights are looked up when a tile is cut (1 byte per pixel instead of 4)."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("resdepth_amd.GpuPatchSampler needs a HIP device (no CPU fallback)")
@@ -100,6 +106,42 @@ class GpuPatchSampler:
         self.tile, self.nodata = int(tile_size), float(nodata)
         self.dsm_std, self.ortho_mean, self.ortho_std = float(dsm_std), ortho_mean, float(ortho_std)
         self.device = dev
+        self.weight, self.weight_table, self.weight_kind = self._check_weights(weight_raster, class_weights)
+
+    def _check_weights(self, raster, table):
+        """-> (device raster | None, device table of _lib.WEIGHT_TABLE floats | None, kind code | None)"""
+        if raster is None:
+            if table is not None:
+                raise ValueError("GpuPatchSampler: class_weights needs the uint8 class raster as weight_raster")
+            return None, None, None
+        dev = self.device
+        if table is None:
+            w = torch.as_tensor(raster)
+            if not w.dtype.is_floating_point:
+                raise ValueError(f"GpuPatchSampler: weight_raster of dtype {w.dtype} needs class_weights (a float raster holds "
+                                 "the weights themselves)")
+            w = w.to(torch.float32).to(dev).contiguous()
+            if tuple(w.shape) != (self.h, self.w):
+                raise ValueError(f"GpuPatchSampler: weight_raster of shape {tuple(w.shape)}, the rasters are {self.h} x {self.w}")
+            if not bool((torch.isfinite(w) & (w >= 0)).all()):
+                raise ValueError("GpuPatchSampler: weight_raster must be finite and >= 0 everywhere")
+            return w, None, _lib.WEIGHT_KINDS["f32"]
+        tab = np.asarray(table, dtype=np.float64).reshape(-1)
+        if not 1 <= tab.size <= _lib.WEIGHT_TABLE:
+            raise ValueError(f"GpuPatchSampler: class_weights holds {tab.size} weights (1..{_lib.WEIGHT_TABLE})")
+        if not bool((np.isfinite(tab) & (tab >= 0)).all()):
+            raise ValueError("GpuPatchSampler: class_weights must be finite and >= 0")
+        c = torch.as_tensor(raster)
+        if c.dtype != torch.uint8:
+            raise ValueError(f"GpuPatchSampler: with class_weights the weight_raster holds uint8 classes (got {c.dtype})")
+        c = c.to(dev).contiguous()
+        if tuple(c.shape) != (self.h, self.w):
+            raise ValueError(f"GpuPatchSampler: weight_raster of shape {tuple(c.shape)}, the rasters are {self.h} x {self.w}")
+        if int(c.max()) >= tab.size:
+            raise ValueError(f"GpuPatchSampler: class {int(c.max())} in weight_raster, class_weights holds {tab.size} weights")
+        full = np.zeros(_lib.WEIGHT_TABLE, dtype=np.float32)
+        full[:tab.size] = tab.astype(np.float32)
+        return c, torch.from_numpy(full).to(dev), _lib.WEIGHT_KINDS["class_u8"]
 
     def sample(self, positions, pairs=None, aug=None):
         """positions: int [n,2] (y, x); pairs: int [n,V] plane indices into `orthos`; aug: int [n,3] (k, flip_v, flip_h)
@@ -463,6 +505,8 @@ def _check_loader_args(who, datasets, input_channels, batch_size, shard):
         raise ValueError(f"{who}: the samplers must share tile size and device")
     if len({s.dsm_gt is None for s in samplers}) != 1:
         raise ValueError(f"{who}: either every sampler or none has a ground-truth raster")
+    if len({s.weight is None for s in samplers}) != 1:
+        raise ValueError(f"{who}: either every sampler or none has a weight raster")
     return datasets, samplers, views, shard
 
 
@@ -488,10 +532,29 @@ def _raster_desc(samplers, views, transform_orthos, with_gt):
     return desc
 
 
-def _assemble_train(desc, n_rasters, tab, v, dsm_channel, t, with_gt, meta):
+_WEIGHT_DESC = [("plane", "<u8"), ("table", "<u8"), ("kind", "<i4"), ("height", "<i4"), ("width", "<i4"), ("reserved", "<i4")]
+# rd_weight_raster (include/resdepth_hip_wloss.h), 32 bytes
+
+
+def _weight_desc(samplers):
+    """The rd_weight_raster table of rd_assemble_train_weights, one row per sampler in the order of _raster_desc, as a uint8
+    device tensor; None when the samplers carry no weights."""
+    s0 = samplers[0]
+    if s0.weight is None:
+        return None
+    desc = np.zeros(len(samplers), dtype=_WEIGHT_DESC)
+    for r, s in zip(desc, samplers):
+        r["plane"], r["table"] = s.weight.data_ptr(), (s.weight_table.data_ptr() if s.weight_table is not None else 0)
+        r["kind"], r["height"], r["width"] = s.weight_kind, s.h, s.w
+    with torch.cuda.device(s0.device):
+        return torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(s0.device)
+
+
+def _assemble_train(desc, n_rasters, tab, v, dsm_channel, t, with_gt, meta, wdesc=None):
     """One rd_assemble_train_patches launch on the current stream for the n samples of the device table `tab` (int32
     [rows, n]) -> the batch dict of GpuTrainSet and GpuValSet: dsm_std / nodata are views of the table, `meta` holds the
-    caller's _META columns."""
+    caller's _META columns.  wdesc (the samplers' _weight_desc): one rd_assemble_train_weights launch over the same table adds
+    `loss_weight` [n, 1, t, t]."""
     n, dev = tab.shape[1], tab.device
     inp = torch.empty(n, dsm_channel + v, t, t, dtype=torch.float32, device=dev)
     mean = torch.empty(n, dtype=torch.float32, device=dev)
@@ -505,6 +568,8 @@ def _assemble_train(desc, n_rasters, tab, v, dsm_channel, t, with_gt, meta):
     batch = {"input": inp, "dsm_mean": mean, "dsm_std": tab[6].view(torch.float32), "nodata": tab[7].view(torch.float32), **meta}
     if with_gt:
         batch["target"], batch["loss_mask"] = tgt, msk.view(torch.bool)
+    if wdesc is not None:
+        batch["loss_weight"] = ops.assemble_train_weights(wdesc, n_rasters, tab, v, t)
     return batch
 
 
@@ -578,6 +643,7 @@ class GpuTrainSet:
             if views:
                 planes.append(pairs[pi])
         desc = _raster_desc(samplers, views, transform_orthos, self.has_gt)
+        self._wdesc = _weight_desc(samplers)
         self.views = n_views or 0
         self._cols = np.concatenate(cols, axis=1)                                        # [8, m], static columns
         self._planes = np.concatenate(planes, axis=0) if views else np.zeros((self._cols.shape[1], 0), dtype=np.int32)
@@ -620,7 +686,8 @@ class GpuTrainSet:
         if nan is None:
             nan = self._nan[n] = torch.full((n,), float("nan"), dtype=torch.float64, device=self.device)
         meta = dict(zip(_META, (tab[1].to(torch.int64), tab[2].to(torch.int64), nan, nan, nan, nan)))
-        return _assemble_train(self._desc, len(self.samplers), tab, self.views, self.dsm_channel, self.tile, self.has_gt, meta)
+        return _assemble_train(self._desc, len(self.samplers), tab, self.views, self.dsm_channel, self.tile, self.has_gt, meta,
+                               self._wdesc)
 
     def epoch_tables(self):
         """One epoch's draws from `generator` -> [host sample table per batch] (pinned int32 [8 + V, n] each): the order
@@ -716,6 +783,7 @@ class GpuValSet:
             areas.append((xe, ye, len(pairs) if views else 1))
             pair_tabs.append(pairs)
         desc = _raster_desc(samplers, views, transform_orthos, True)
+        self._wdesc = _weight_desc(samplers)
         self.views = v = n_views or 0
         used_stride, ids, pos, reg, pidx = tiling.concat_val_samples(areas, t, stride, views)
         ids, pidx = np.array(ids, dtype=np.int64), np.array(pidx, dtype=np.int64)
@@ -769,7 +837,8 @@ class GpuValSet:
         j0, j1 = int(self._first[k]), int(self._first[k + 1])
         tab = self._table[j0 * self._rows:j1 * self._rows].view(self._rows, j1 - j0)
         meta = {key: col[j0:j1] for key, col in self._meta.items()}
-        return _assemble_train(self._desc, len(self.samplers), tab, self.views, self.dsm_channel, self.tile, True, meta)
+        return _assemble_train(self._desc, len(self.samplers), tab, self.views, self.dsm_channel, self.tile, True, meta,
+                               self._wdesc)
 
     def __iter__(self):
         yield from _prefetched(self.device, range(len(self._bounds)), self._assemble, self.prefetch)

@@ -13,6 +13,9 @@ What is different underneath:
     nn.SmoothL1Loss (reduction='mean') and resdepth_amd.MaskedLoss (which adds the slope-consistency term).  Whatever is
     optimised, `MAE_metric` stays the masked MAE in both phases, so best-model selection, ReduceLROnPlateau and the
     checkpoints' loss_val compare across criteria; the train phase logs the optimised value as `loss` beside it;
+  * a batch may carry per-pixel loss weights as `loss_weight` ([N,1,H,W] fp32; GpuTrainSet / GpuValSet add it when their
+    samplers hold weight rasters): both phases pass it to the fused loss (for nn.L1Loss too, through a MaskedLoss built when
+    the first weight arrives), `MAE_metric` stays the unweighted masked MAE;
   * the epoch loop keeps the per-step loss on the device and reads it back only when a value is logged
     (every `freq_average_train_loss` iterations and at epoch end) instead of one host sync per step
     (lib/Trainer.py:197); `inference_one_batch` still returns a python float as the reference does;
@@ -105,7 +108,7 @@ class DevicePrefetcher:
     Iterating it yields the loader's batch dicts with those five fields replaced by device tensors; everything else
     (offsets, nodata, valid-pixel boxes) is handed on as the loader produced it."""
 
-    FIELDS = ("input", "target", "loss_mask")
+    FIELDS = ("input", "target", "loss_mask", "loss_weight")      # loss_weight: only where the loader's batches carry it
     SCALARS = ("dsm_mean", "dsm_std")
 
     def __init__(self, loader, device, depth: int = 1):
@@ -199,6 +202,7 @@ class Trainer:
         self.grad_sync = getattr(self.model, "grad_sync", None)
         # anything but plain L1: the optimised value and the masked MAE come out of one fused call (loss.MaskedLoss.last_mae)
         self._loss_module = None if plain_l1 else MaskedLoss(kind, delta, slope_weight, grad_sync=self.grad_sync)
+        self._loss_spec = (kind, delta, slope_weight)
         self._last_mae = None
         # host -> device staging of the next batch under the current step (DevicePrefetcher); 0 = the copies ride the compute
         # stream in front of the forward, as in r04
@@ -224,6 +228,8 @@ class Trainer:
 
         first = next(iter(self.loader["train"]))          # the reference also draws one batch here (lib/Trainer.py:61-64)
         self.batch_size = first["input"].shape[0]
+        if isinstance(first, dict) and first.get("loss_weight") is not None:
+            self._weighted_module()               # per-pixel weights: the train phase meters the weighted value as `loss`
         if self.is_dist and self.grad_sync is not None:
             # every step issues collectives (loss normaliser, gradients, SyncBN): ranks with a different number of
             # batches would deadlock, a different batch size would bias the SyncBN statistics
@@ -294,6 +300,13 @@ class Trainer:
         torch.save(state, filepath)
 
     # ------------------------------------------------------------------------------------------
+    def _weighted_module(self):
+        """The MaskedLoss that takes a batch's `loss_weight`: the criterion's own, or -- plain L1, which has no weighted form
+        among the masked_l1 kernels -- one built when the first weight arrives."""
+        if self._loss_module is None:
+            self._loss_module = MaskedLoss(*self._loss_spec, grad_sync=self.grad_sync)
+        return self._loss_module
+
     def _loss_on_device(self, batch, train: bool):
         """forward (+ backward when training); returns the 0-dim device loss (no host sync) and leaves the batch's masked MAE
         in `_last_mae` (plain L1: the loss itself)."""
@@ -303,20 +316,27 @@ class Trainer:
         loss_mask = loss_mask.to(self.device, non_blocking=True)
         mean = torch.flatten(batch["dsm_mean"])
         std = torch.flatten(batch["dsm_std"])
+        weight = batch.get("loss_weight") if isinstance(batch, dict) else None
+        if weight is not None:
+            weight = weight.to(self.device, non_blocking=True)
         if train:
             self.model.train()
             y_pred = self.model(x)
-            loss = self._criterion_on_device(y_pred, y, loss_mask, mean, std)
+            loss = self._criterion_on_device(y_pred, y, loss_mask, mean, std, weight)
             loss.backward()
         else:
             self.model.eval()
             with torch.no_grad():
                 y_pred = self.model(x)
-                loss = self._criterion_on_device(y_pred, y, loss_mask, mean, std)
+                loss = self._criterion_on_device(y_pred, y, loss_mask, mean, std, weight)
         return loss.detach()
 
-    def _criterion_on_device(self, y_pred, y, loss_mask, mean, std):
-        if self._loss_module is None:
+    def _criterion_on_device(self, y_pred, y, loss_mask, mean, std, weight=None):
+        if weight is not None:
+            module = self._weighted_module()
+            loss = module(y_pred, y, loss_mask, mean, std, weight=weight)
+            self._last_mae = module.last_mae
+        elif self._loss_module is None:
             loss = masked_l1_loss(y_pred, y, loss_mask, mean, std, grad_sync=self.grad_sync)
             self._last_mae = loss.detach()
         else:
@@ -376,8 +396,10 @@ class Trainer:
                 x, y, loss_mask = self._extract_inputs_outputs_loss_masks(batch)
                 to = lambda t, dt=None: t.to(self.device, dtype=dt, non_blocking=True)      # noqa: E731
                 # .clone(): after a replay the loss is the graph's own output buffer, rewritten by the next one
+                weight = batch.get("loss_weight") if isinstance(batch, dict) else None
                 loss = graphed(to(x), to(y), to(loss_mask), to(torch.flatten(batch["dsm_mean"]), torch.float32),
-                               to(torch.flatten(batch["dsm_std"]), torch.float32)).clone()
+                               to(torch.flatten(batch["dsm_std"]), torch.float32),
+                               weight=None if weight is None else to(weight)).clone()
                 self._last_mae = loss if self._loss_module is None else graphed.mae.clone()
             else:
                 loss = self._loss_on_device(batch, phase == "train")

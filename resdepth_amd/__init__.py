@@ -17,6 +17,7 @@ from . import normalization  # noqa: F401
 from .evaluation import (dilate_mask, dsm_slope, error_map, evaluate_binned, evaluate_pairs_performance,  # noqa: F401
                          evaluate_pairs_statistics, evaluate_performance, evaluate_statistics, get_statistics_masked,
                          print_binned, print_statistics)
+from .coregistration import coregister, estimate_shift, translate  # noqa: F401
 from .factories import (get_loss, get_model, get_scheduler, get_trainer, valid_tile_size,  # noqa: F401
                         validate_tile_size)
 
@@ -24,4 +25,5 @@ __all__ = ["UNet", "SkipConnection", "MaskedL1Loss", "masked_l1_loss", "MaskedLo
            "SyntheticDsmOrthoDataset", "synthetic_batch", "predict_linear_blend", "SyntheticRasterTiles", "predict_pairs_linear_blend", "PairSweep",
            "GpuPatchSampler", "SamplerLoader", "GpuGridTiles", "GpuTrainSet", "GpuValSet", "normalization", "get_loss", "get_model", "get_scheduler", "get_trainer", "valid_tile_size", "validate_tile_size",
            "dilate_mask", "evaluate_statistics", "evaluate_performance", "print_statistics", "get_statistics_masked",
-           "evaluate_pairs_statistics", "evaluate_pairs_performance", "dsm_slope", "error_map", "evaluate_binned", "print_binned"]
+           "evaluate_pairs_statistics", "evaluate_pairs_performance", "dsm_slope", "error_map", "evaluate_binned", "print_binned",
+           "estimate_shift", "coregister", "translate"]

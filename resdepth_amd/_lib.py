@@ -222,6 +222,14 @@ SIGNATURES_WLOSS = {
 # the constants of that header
 WEIGHT_KINDS = {"f32": 0, "class_u8": 1}
 WEIGHT_TABLE = 256
+# include/resdepth_hip_coreg.h (co-registration: sums of the 3-D translation fit, bilinear sub-pixel resampler), one to one as above
+SIGNATURES_COREG = {
+    "rd_shift_sums_ws_bytes": (SZ, [I, I]),
+    "rd_shift_sums": (I, [P, I, P, I, P, I, I, I, D, D, D, D, D, P, SZ, P, P]),
+    "rd_translate_bilinear": (I, [P, I, I, I, D, D, D, D, D, P, P]),
+}
+# the constants of that header
+SHIFT_NSUMS, SHIFT_MAX_BLOCKS, SHIFT_MAX_TILES = 10, 2048, 1 << 30
 
 
 class ProfEntry(C.Structure):
@@ -245,7 +253,7 @@ def load():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
                 + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()) \
                 + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()) + list(SIGNATURES_TAIL.items()) \
-                + list(SIGNATURES_WLOSS.items()):
+                + list(SIGNATURES_WLOSS.items()) + list(SIGNATURES_COREG.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

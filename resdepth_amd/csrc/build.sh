@@ -18,17 +18,17 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 #      0.3-0.6 % end to end (r03 interleaved A/B, profiles/r03_notes.md).
 BASE="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -fno-slp-vectorize -Wall -Wno-unused-result $RD_EXTRA_FLAGS"
 FLAGS="$BASE -mllvm -amdgpu-mfma-vgpr-form"
-# RD_CLEAN=1 (what __graft_entry__.build() sets): drop every object first, so "does it build" compiles all eleven translation
+# RD_CLEAN=1 (what __graft_entry__.build() sets): drop every object first, so "does it build" compiles all twelve translation
 # units from source instead of re-linking whatever obj/ holds
 [ -n "$RD_CLEAN" ] && rm -rf "$OBJ"
 mkdir -p "$OBJ"
 # the translation units, and the headers whose change rebuilds every object
-UNITS="rd_runtime rd_igemm rd_convt rd_wgrad_strip rd_elementwise rd_tiles rd_edge_conv rd_stats rd_trainset rd_loss rd_optim"
+UNITS="rd_runtime rd_igemm rd_convt rd_wgrad_strip rd_elementwise rd_tiles rd_edge_conv rd_stats rd_trainset rd_loss rd_optim rd_coreg"
 INC="$HERE/../../include"
 HEADERS=("$HERE/rd_common.h" "$HERE/rd_mfma_dev.h" "$HERE/rd_nt.h" "$HERE/rd_tile_dev.h" "$INC/resdepth_hip.h"
          "$INC/resdepth_hip_tta.h" "$INC/resdepth_hip_pairs.h" "$INC/resdepth_hip_eval.h" "$INC/resdepth_hip_loss.h"
          "$INC/resdepth_hip_optim.h" "$INC/resdepth_hip_dist.h" "$INC/resdepth_hip_errmap.h"
-         "$INC/resdepth_hip_tail.h" "$INC/resdepth_hip_wloss.h")
+         "$INC/resdepth_hip_tail.h" "$INC/resdepth_hip_wloss.h" "$INC/resdepth_hip_coreg.h")
 pids=()
 objs=()
 for f in $UNITS; do

@@ -230,6 +230,14 @@ SIGNATURES_COREG = {
 }
 # the constants of that header
 SHIFT_NSUMS, SHIFT_MAX_BLOCKS, SHIFT_MAX_TILES = 10, 2048, 1 << 30
+# include/resdepth_hip_edt.h (exact squared Euclidean distance transform with feature transform, nearest-valid fill), one to one as above
+SIGNATURES_EDT = {
+    "rd_edt_ws_bytes": (SZ, [I, I]),
+    "rd_edt_sq": (I, [P, I, I, I, P, P, P, SZ, P]),
+    "rd_fill_nearest": (I, [P, I, P, P, LL, I, P, P]),
+}
+# the constants of that header
+EDT_MAX_ROWS, EDT_MAX_COLS, EDT_NONE, EDT_BAND_ROWS = 32768, 16384, 2147483647, 128
 
 
 class ProfEntry(C.Structure):
@@ -253,7 +261,7 @@ def load():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
                 + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()) \
                 + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()) + list(SIGNATURES_TAIL.items()) \
-                + list(SIGNATURES_WLOSS.items()) + list(SIGNATURES_COREG.items()):
+                + list(SIGNATURES_WLOSS.items()) + list(SIGNATURES_COREG.items()) + list(SIGNATURES_EDT.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -1447,6 +1447,192 @@ int rd_fuse_planes(const double* planes, long long plane_stride, int n_planes, l
 
 }  // extern "C"
 
+// ---- the exact squared Euclidean distance transform with its feature transform, and the nearest-valid fill
+// (include/resdepth_hip_edt.h).  Integer arithmetic only, no atomics.  The column pass: edt_band_kernel scans every band of
+// RD_EDT_BAND_ROWS rows of every column downwards (one thread per band and column, threads along the columns, so a wave reads and
+// writes consecutive addresses), leaves the nearest set row at or above each pixel INSIDE the band in d2's storage (-1: none) and
+// the band's first and last set row in ws; edt_column_kernel finds the nearest set rows beyond its band by walking ws, scans the
+// band upwards and replaces what d2 holds by the signed row offset to the nearest set pixel of the column, the upper one on a tie
+// (RD_EDT_NONE: the column is empty).  The row pass: edt_row_kernel, one block per row, stages the row's offsets in LDS as int16
+// BEFORE anything is written (d2 is updated in place), then every pixel searches outward from its own column.
+namespace rd {
+
+constexpr int EDT_THREADS = 256;
+constexpr int EDT_NONE16 = -32768;                     // "no set pixel in this column" among int16 offsets: |offset| <= 32767
+static_assert(RD_EDT_MAX_ROWS <= 32768, "a row offset fits an int16 beside EDT_NONE16");
+static_assert((long)RD_EDT_MAX_ROWS * RD_EDT_MAX_ROWS + (long)RD_EDT_MAX_COLS * RD_EDT_MAX_COLS < 2147483647l, "d2 stays int32");
+static_assert((long)RD_EDT_MAX_ROWS * RD_EDT_MAX_COLS < 2147483648l, "idx stays int32");
+static_assert(RD_EDT_MAX_COLS * 2 <= 65536, "a row of offsets fits the LDS of one block");
+
+__global__ __launch_bounds__(EDT_THREADS) void edt_band_kernel(const uint8_t* __restrict__ mask, int invert, int rows, int cols,
+                                                               int bands, int32_t* __restrict__ d2, int32_t* __restrict__ ws) {
+    const int c = blockIdx.x * EDT_THREADS + threadIdx.x, b = blockIdx.y;
+    if (c >= cols) return;
+    const int r0 = b * RD_EDT_BAND_ROWS, r1 = min(rows, r0 + RD_EDT_BAND_ROWS);
+    int first = -1, last = -1;
+    for (int r = r0; r < r1; ++r) {
+        const size_t i = (size_t)r * cols + c;
+        if ((mask[i] != 0) != (invert != 0)) {
+            if (first < 0) first = r;
+            last = r;
+        }
+        d2[i] = last;
+    }
+    ws[(size_t)b * cols + c] = first;
+    ws[(size_t)(bands + b) * cols + c] = last;
+}
+
+__global__ __launch_bounds__(EDT_THREADS) void edt_column_kernel(int rows, int cols, int bands, int32_t* __restrict__ d2,
+                                                                 const int32_t* __restrict__ ws) {
+    const int c = blockIdx.x * EDT_THREADS + threadIdx.x, b = blockIdx.y;
+    if (c >= cols) return;
+    const int r0 = b * RD_EDT_BAND_ROWS, r1 = min(rows, r0 + RD_EDT_BAND_ROWS);
+    int up = -1, next = -1;                            // the nearest set rows of the column above and below the band
+    for (int bb = b - 1; bb >= 0 && up < 0; --bb) up = ws[(size_t)(bands + bb) * cols + c];
+    for (int bb = b + 1; bb < bands && next < 0; ++bb) next = ws[(size_t)bb * cols + c];
+    for (int r = r1 - 1; r >= r0; --r) {
+        const size_t i = (size_t)r * cols + c;
+        int u = d2[i];
+        if (u < 0) u = up;
+        if (u == r) next = r;
+        int off = RD_EDT_NONE;
+        if (u >= 0 && (next < 0 || r - u <= next - r))
+            off = u - r;                               // the upper pixel wins a tie
+        else if (next >= 0)
+            off = next - r;
+        d2[i] = off;
+    }
+}
+
+__global__ __launch_bounds__(EDT_THREADS) void edt_row_kernel(int cols, int32_t* __restrict__ d2, int32_t* __restrict__ idx) {
+    extern __shared__ short edt_offs[];                // cols int16 offsets
+    const int r = blockIdx.x;
+    const size_t base = (size_t)r * cols;
+    int any = 0;
+    for (int c = threadIdx.x; c < cols; c += EDT_THREADS) {
+        const int v = d2[base + c];
+        edt_offs[c] = (short)(v == RD_EDT_NONE ? EDT_NONE16 : v);
+        any |= v != RD_EDT_NONE;
+    }
+    // the barrier between staging and writing, and the vote: a row without an offset means a mask without a set pixel
+    if (!__syncthreads_or(any)) {
+        for (int c = threadIdx.x; c < cols; c += EDT_THREADS) {
+            d2[base + c] = RD_EDT_NONE;
+            if (idx) idx[base + c] = -1;
+        }
+        return;
+    }
+    for (int c = threadIdx.x; c < cols; c += EDT_THREADS) {
+        int best = RD_EDT_NONE, bc = c;
+        int g = edt_offs[c];
+        if (g != EDT_NONE16) best = g * g;
+        const int reach = max(c, cols - 1 - c);        // beyond it both neighbours lie outside the row
+        for (int dx = 1; dx <= reach && dx * dx < best; ++dx) {
+            const int l = c - dx, rt = c + dx;
+            if (l >= 0) {
+                g = edt_offs[l];
+                const int d = dx * dx + g * g;
+                if (g != EDT_NONE16 && d < best) {
+                    best = d;
+                    bc = l;
+                }
+            }
+            if (rt < cols) {
+                g = edt_offs[rt];
+                const int d = dx * dx + g * g;
+                if (g != EDT_NONE16 && d < best) {
+                    best = d;
+                    bc = rt;
+                }
+            }
+        }
+        d2[base + c] = best;
+        if (idx) idx[base + c] = best == RD_EDT_NONE ? -1 : (r + (int)edt_offs[bc]) * cols + bc;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fill_nearest_kernel(const T* __restrict__ dsm, const int32_t* __restrict__ d2,
+                                                           const int32_t* __restrict__ idx, long n, int max_d2,
+                                                           T* __restrict__ out) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int d = d2[i], j = idx[i];
+        const bool take = d > 0 && d <= max_d2 && j >= 0 && (long)j < n;
+        out[i] = dsm[take ? (long)j : i];
+    }
+}
+
+static bool edt_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+static bool edt_shape_ok(int rows, int cols) {
+    return rows >= 1 && cols >= 1 && rows <= RD_EDT_MAX_ROWS && cols <= RD_EDT_MAX_COLS;
+}
+
+static int edt_bands(int rows) { return (rows + RD_EDT_BAND_ROWS - 1) / RD_EDT_BAND_ROWS; }
+
+}  // namespace rd
+
+extern "C" {
+
+size_t rd_edt_ws_bytes(int rows, int cols) {
+    if (!edt_shape_ok(rows, cols)) return 0;
+    return (size_t)edt_bands(rows) * cols * 2 * sizeof(int32_t);
+}
+
+int rd_edt_sq(const uint8_t* mask, int invert, int rows, int cols, int32_t* d2, int32_t* idx, void* ws, size_t ws_bytes,
+              rd_stream_t s_) {
+    RD_REQUIRE(mask && d2 && ws, "rd_edt_sq: null pointer");
+    RD_REQUIRE(edt_shape_ok(rows, cols), "rd_edt_sq: bad shape (rows=%d cols=%d; 1..%d x 1..%d)", rows, cols, RD_EDT_MAX_ROWS,
+               RD_EDT_MAX_COLS);
+    const size_t want = rd_edt_ws_bytes(rows, cols), n = (size_t)rows * cols;
+    RD_REQUIRE(ws_bytes >= want, "rd_edt_sq: workspace of %zu bytes, %zu needed", ws_bytes, want);
+    RD_REQUIRE(!edt_overlap(mask, n, d2, 4 * n) && !(idx && edt_overlap(mask, n, idx, 4 * n)),
+               "rd_edt_sq: d2 or idx overlaps the mask");
+    RD_REQUIRE(!(idx && edt_overlap(d2, 4 * n, idx, 4 * n)), "rd_edt_sq: d2 and idx overlap");
+    hipStream_t s = (hipStream_t)s_;
+    const int bands = edt_bands(rows);
+    const dim3 grid((cols + EDT_THREADS - 1) / EDT_THREADS, bands);
+    {
+        // algorithmic bytes: the mask read, the in-band rows written and read, the offsets written
+        ProfScope ps(s, "edt_columns", 0, 13.0 * (double)n);
+        RD_LAUNCH(edt_band_kernel, grid, dim3(EDT_THREADS), 0, s, mask, invert ? 1 : 0, rows, cols, bands, d2, (int32_t*)ws);
+        RD_LAUNCH_CHECK("edt_band");
+        RD_LAUNCH(edt_column_kernel, grid, dim3(EDT_THREADS), 0, s, rows, cols, bands, d2, (const int32_t*)ws);
+        RD_LAUNCH_CHECK("edt_column");
+    }
+    {
+        // the offsets read, d2 and idx written
+        ProfScope ps(s, "edt_rows", 0, (idx ? 12.0 : 8.0) * (double)n);
+        RD_LAUNCH(edt_row_kernel, dim3((unsigned)rows), dim3(EDT_THREADS), (size_t)cols * sizeof(short), s, cols, d2, idx);
+        RD_LAUNCH_CHECK("edt_row");
+    }
+    return RD_OK;
+}
+
+int rd_fill_nearest(const void* dsm, int dsm_f64, const int32_t* d2, const int32_t* idx, long long n, int max_d2, void* out,
+                    rd_stream_t s_) {
+    RD_REQUIRE(dsm && d2 && idx && out, "rd_fill_nearest: null pointer");
+    RD_REQUIRE(n >= 1, "rd_fill_nearest: n = %lld", n);
+    RD_REQUIRE(max_d2 >= 0, "rd_fill_nearest: max_d2 %d is negative", max_d2);
+    const size_t width = dsm_f64 ? 8 : 4;
+    RD_REQUIRE(!edt_overlap(dsm, width * (size_t)n, out, width * (size_t)n), "rd_fill_nearest: out overlaps dsm");
+    hipStream_t s = (hipStream_t)s_;
+    ProfScope ps(s, "fill_nearest", 0, (double)n * (8.0 + 2.0 * width));
+    if (dsm_f64)
+        RD_LAUNCH(fill_nearest_kernel<uint64_t>, dim3(stats_grid((long)n)), dim3(256), 0, s, (const uint64_t*)dsm, d2, idx, (long)n,
+                  max_d2, (uint64_t*)out);
+    else
+        RD_LAUNCH(fill_nearest_kernel<uint32_t>, dim3(stats_grid((long)n)), dim3(256), 0, s, (const uint32_t*)dsm, d2, idx, (long)n,
+                  max_d2, (uint32_t*)out);
+    RD_LAUNCH_CHECK("fill_nearest");
+    return RD_OK;
+}
+
+}  // extern "C"
+
 // ---- where the error is and on what ground (include/resdepth_hip_errmap.h) -------------------------------------------------
 // cell_stats_kernel: the statistics engine turned inside out -- not few sets of many values with global histograms and a launch
 // per pass, but one block per cell with everything in the block.  The moments are SetMoments with one set (a thread adds its

@@ -654,4 +654,5 @@ int rd_prof_collect(rd_prof_entry* out, int max_entries); /* returns number of c
 #include "resdepth_hip_wloss.h" /* per-pixel weights for the masked training losses, weight tiles from HBM rasters */
 #include "resdepth_hip_coreg.h" /* co-registration: the sums of the 3-D translation fit, the bilinear sub-pixel resampler */
 #include "resdepth_hip_edt.h" /* exact squared Euclidean distance transform with feature transform, nearest-valid fill */
+#include "resdepth_hip_ortho.h" /* ortho-rectification of satellite views onto the DSM grid through their RPC camera models */
 #endif /* RESDEPTH_HIP_H */

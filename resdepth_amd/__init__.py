@@ -19,6 +19,7 @@ from .evaluation import (dilate_mask, dsm_slope, error_map, evaluate_binned, eva
                          print_binned, print_statistics)
 from .coregistration import coregister, estimate_shift, translate  # noqa: F401
 from .morphology import buffer_mask, distance_transform, edge_distance, fill_voids  # noqa: F401
+from .ortho import RPC, orthorectify, project_grid  # noqa: F401
 from .factories import (get_loss, get_model, get_scheduler, get_trainer, valid_tile_size,  # noqa: F401
                         validate_tile_size)
 
@@ -27,4 +28,5 @@ __all__ = ["UNet", "SkipConnection", "MaskedL1Loss", "masked_l1_loss", "MaskedLo
            "GpuPatchSampler", "SamplerLoader", "GpuGridTiles", "GpuTrainSet", "GpuValSet", "normalization", "get_loss", "get_model", "get_scheduler", "get_trainer", "valid_tile_size", "validate_tile_size",
            "dilate_mask", "evaluate_statistics", "evaluate_performance", "print_statistics", "get_statistics_masked",
            "evaluate_pairs_statistics", "evaluate_pairs_performance", "dsm_slope", "error_map", "evaluate_binned", "print_binned",
-           "estimate_shift", "coregister", "translate", "distance_transform", "edge_distance", "buffer_mask", "fill_voids"]
+           "estimate_shift", "coregister", "translate", "distance_transform", "edge_distance", "buffer_mask", "fill_voids",
+           "RPC", "orthorectify", "project_grid"]

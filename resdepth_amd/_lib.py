@@ -238,6 +238,15 @@ SIGNATURES_EDT = {
 }
 # the constants of that header
 EDT_MAX_ROWS, EDT_MAX_COLS, EDT_NONE, EDT_BAND_ROWS = 32768, 16384, 2147483647, 128
+# include/resdepth_hip_ortho.h (ortho-rectification of satellite views onto the DSM grid through RPC camera models), one to one as above
+SIGNATURES_ORTHO = {
+    "rd_ortho_rpc": (I, [P, I, I, D, D, D, D, I, D, D, D, D, P, I, I, F, P, P, P, P]),
+}
+# the constants of that header
+ORTHO_MAX_VIEWS, ORTHO_VIEW_BYTES = 16, 776
+ORTHO_DTYPES = {"uint8": 0, "uint16": 1, "float32": 2}
+ORTHO_CRS = {"geographic": 0, "utm": 1}
+ORTHO_RESAMPLING = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 
 
 class ProfEntry(C.Structure):
@@ -261,7 +270,8 @@ def load():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_TTA.items()) + list(SIGNATURES_PAIRS.items()) \
                 + list(SIGNATURES_EVAL.items()) + list(SIGNATURES_LOSS.items()) + list(SIGNATURES_OPTIM.items()) \
                 + list(SIGNATURES_DIST.items()) + list(SIGNATURES_ERRMAP.items()) + list(SIGNATURES_TAIL.items()) \
-                + list(SIGNATURES_WLOSS.items()) + list(SIGNATURES_COREG.items()) + list(SIGNATURES_EDT.items()):
+                + list(SIGNATURES_WLOSS.items()) + list(SIGNATURES_COREG.items()) + list(SIGNATURES_EDT.items()) \
+                + list(SIGNATURES_ORTHO.items()):
             fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -29,7 +29,7 @@ HEADERS=("$HERE/rd_common.h" "$HERE/rd_mfma_dev.h" "$HERE/rd_nt.h" "$HERE/rd_til
          "$INC/resdepth_hip_tta.h" "$INC/resdepth_hip_pairs.h" "$INC/resdepth_hip_eval.h" "$INC/resdepth_hip_loss.h"
          "$INC/resdepth_hip_optim.h" "$INC/resdepth_hip_dist.h" "$INC/resdepth_hip_errmap.h"
          "$INC/resdepth_hip_tail.h" "$INC/resdepth_hip_wloss.h" "$INC/resdepth_hip_coreg.h"
-         "$INC/resdepth_hip_edt.h")
+         "$INC/resdepth_hip_edt.h" "$INC/resdepth_hip_ortho.h")
 pids=()
 objs=()
 for f in $UNITS; do

@@ -3,6 +3,7 @@
 //     predicted in any of the square's eight orientations (test-time augmentation) and into one raster per image pair;
 //   * training samples of one raster: per-patch sums and the assembled, augmented patches (GpuPatchSampler);
 //   * validation / inference grid tiles (lib/DsmOrthoDataset.py:161-291, sampling_strategy 'val' / 'test'), plain and oriented.
+//   * the ortho planes themselves: raw views ortho-rectified onto the DSM grid through their RPC camera models (last section).
 // Training batches that mix several rasters are rd_trainset.hip's; the pieces both share (the D4 maps, the four-pixel blocks,
 // the 256-leaf tree, a tile's means) live in rd_tile_dev.h, once.  All of it is HBM-bound gather / scatter with fixed-order
 // fp64 sums: no float atomics, results independent of the launch shape.
@@ -555,6 +556,238 @@ int rd_assemble_grid_tiles_aug(const float* dsm_in, const float* dsm_gt, const f
               tile / GRID_SLAB_ROWS, dsm_mode, dsm_mean, dsm_std, ortho_mode, ortho_mean, ortho_std, (const double*)ws, aug, input,
               dsm_mean_out);
     RD_LAUNCH_CHECK("grid_tile_write_aug");
+    return RD_OK;
+}
+
+}  // extern "C"
+
+// ---- ortho-rectification through RPC camera models (include/resdepth_hip_ortho.h) ------------------------------------------------
+// What makes the ortho planes the kernels above cut tiles from.  ortho_rpc_kernel: one thread per DSM pixel takes the ground point
+// to degrees once (the inverse Krueger series for a UTM grid) and walks the views: the rational polynomial projection in fp64,
+// then a gather of up to 16 taps of the image.  The model is read through wave-uniform addresses (scalar loads), the taps go
+// through the cache, and out / valid / coords stream out with non-temporal stores.  Every loop but the one over the views has
+// a compile-time trip count and constant indices, so the monomials and the taps stay in registers: no scratch.
+namespace rd {
+
+// how a wave's 64 pixels lie on the grid (ORTHO_FW x ORTHO_FH) and the four waves of a block beside or above one another
+// (64 x 1, 16 x 4 and 8 x 8 were measured, DESIGN 3.6f: the kernel is bound by its fp64 arithmetic, the first two tie and 8 x 8 is
+// 2-5 % slower; the row of 64 is the one that is built)
+constexpr int ORTHO_FW = 64, ORTHO_FH = 64 / ORTHO_FW;
+constexpr int ORTHO_WX = ORTHO_FW >= 64 ? 1 : 4, ORTHO_WY = 4 / ORTHO_WX;
+constexpr int ORTHO_TW = ORTHO_FW * ORTHO_WX, ORTHO_TH = ORTHO_FH * ORTHO_WY;
+static_assert(ORTHO_FW * ORTHO_FH == 64 && ORTHO_WX * ORTHO_WY == 4, "a block is four waves of 64 pixels");
+static_assert(sizeof(rd_ortho_view) == 776, "rd_ortho_view is packed by resdepth_amd/ortho.py as 776 bytes");
+
+// WGS84 and the Krueger series to n^4
+constexpr double KR_F = 1.0 / 298.257223563, KR_N = KR_F / (2.0 - KR_F), KR_N2 = KR_N * KR_N, KR_N3 = KR_N2 * KR_N, KR_N4 = KR_N2 * KR_N2;
+constexpr double KR_E2 = KR_F * (2.0 - KR_F), KR_E = 0.08181919084262149;       // the first eccentricity and its square
+static_assert(KR_E * KR_E - KR_E2 < 1e-17 && KR_E2 - KR_E * KR_E < 1e-17, "KR_E is the root of KR_E2");
+constexpr double KR_K0A = 0.9996 * (6378137.0 / (1.0 + KR_N) * (1.0 + KR_N2 / 4.0 + KR_N4 / 64.0));
+constexpr double KR_B1 = KR_N / 2.0 - 2.0 * KR_N2 / 3.0 + 37.0 * KR_N3 / 96.0 - KR_N4 / 360.0;
+constexpr double KR_B2 = KR_N2 / 48.0 + KR_N3 / 15.0 - 437.0 * KR_N4 / 1440.0;
+constexpr double KR_B3 = 17.0 * KR_N3 / 480.0 - 37.0 * KR_N4 / 840.0;
+constexpr double KR_B4 = 4397.0 * KR_N4 / 161280.0;
+constexpr double KR_DEG = 57.29577951308232;                                    // 180 / pi
+
+__device__ __forceinline__ void st_nt_u8(uint8_t* p, uint8_t v) {
+#ifdef RD_NO_NT
+    *p = v;
+#else
+    __builtin_nontemporal_store(v, p);
+#endif
+}
+__device__ __forceinline__ void st_nt_f64(double* p, double v) {
+#ifdef RD_NO_NT
+    *p = v;
+#else
+    __builtin_nontemporal_store(v, p);
+#endif
+}
+
+// easting / northing -> degrees
+__device__ __forceinline__ void ortho_utm_inverse(double X, double Y, double lon0_deg, double false_northing, double& lon,
+                                                  double& lat) {
+    const double xi = (Y - false_northing) / KR_K0A, eta = (X - 500000.0) / KR_K0A;
+    double s2, c2;
+    sincos(2.0 * xi, &s2, &c2);
+    const double sh2 = sinh(2.0 * eta), ch2 = cosh(2.0 * eta);
+    // the multiples 4, 6, 8 by the addition theorems
+    const double s4 = 2.0 * s2 * c2, c4 = 1.0 - 2.0 * s2 * s2, sh4 = 2.0 * sh2 * ch2, ch4 = 1.0 + 2.0 * sh2 * sh2;
+    const double s6 = s4 * c2 + c4 * s2, c6 = c4 * c2 - s4 * s2, sh6 = sh4 * ch2 + ch4 * sh2, ch6 = ch4 * ch2 + sh4 * sh2;
+    const double s8 = 2.0 * s4 * c4, c8 = 1.0 - 2.0 * s4 * s4, sh8 = 2.0 * sh4 * ch4, ch8 = 1.0 + 2.0 * sh4 * sh4;
+    const double xip = xi - (KR_B1 * s2 * ch2 + KR_B2 * s4 * ch4 + KR_B3 * s6 * ch6 + KR_B4 * s8 * ch8);
+    const double etap = eta - (KR_B1 * c2 * sh2 + KR_B2 * c4 * sh4 + KR_B3 * c6 * sh6 + KR_B4 * c8 * sh8);
+    double sx, cx;
+    sincos(xip, &sx, &cx);
+    const double she = sinh(etap);
+    const double taup = sx / sqrt(she * she + cx * cx);                          // tangent of the conformal latitude
+    double tau = taup;
+#pragma unroll
+    for (int it = 0; it < 3; ++it) {                                            // Newton on tau = tan(lat)
+        const double root = sqrt(1.0 + tau * tau);
+        const double sigma = sinh(KR_E * atanh(KR_E * tau / root));
+        const double t = tau * sqrt(1.0 + sigma * sigma) - sigma * root;
+        tau += (taup - t) / sqrt(1.0 + t * t) * (1.0 + (1.0 - KR_E2) * tau * tau) / ((1.0 - KR_E2) * root);
+    }
+    lat = atan(tau) * KR_DEG;
+    lon = lon0_deg + atan2(she, cx) * KR_DEG;
+}
+
+__device__ __forceinline__ double ortho_poly(const double* __restrict__ k, const double (&m)[20]) {
+    double s = k[0];
+#pragma unroll
+    for (int i = 1; i < 20; ++i) s += k[i] * m[i];
+    return s;
+}
+
+template <int DT>
+__device__ __forceinline__ double ortho_tap(const void* __restrict__ img, long at) {
+    if (DT == RD_ORTHO_U8) return (double)((const uint8_t*)img)[at];
+    if (DT == RD_ORTHO_U16) return (double)((const uint16_t*)img)[at];
+    return (double)((const float*)img)[at];
+}
+
+// the value at (yi, xi) of a rows x cols image -> whether it is defined.  Nothing outside the image is read: the bounds of the
+// needed taps are settled first, as doubles (NaN and the infinities fail them).
+template <int RS, int DT>
+__device__ __forceinline__ bool ortho_resample(const void* __restrict__ img, long pitch, int rows, int cols, double nd, double yi,
+                                               double xi, double& val) {
+    if (RS == RD_ORTHO_NEAREST) {
+        const double yn = floor(yi + 0.5), xn = floor(xi + 0.5);
+        if (!(yn >= 0.0 && xn >= 0.0 && yn <= (double)(rows - 1) && xn <= (double)(cols - 1))) return false;
+        val = ortho_tap<DT>(img, (long)(int)yn * pitch + (int)xn);
+        return !(val == nd);
+    }
+    const double y0 = floor(yi), x0 = floor(xi);
+    const double fy = yi - y0, fx = xi - x0;
+    const bool two_x = fx != 0.0, two_y = fy != 0.0;
+    if (RS == RD_ORTHO_BILINEAR) {
+        if (!(y0 >= 0.0 && x0 >= 0.0 && y0 <= (double)(rows - (two_y ? 2 : 1)) && x0 <= (double)(cols - (two_x ? 2 : 1)))) return false;
+        const long at = (long)(int)y0 * pitch + (int)x0;
+        const double v00 = ortho_tap<DT>(img, at);
+        const double v01 = two_x ? ortho_tap<DT>(img, at + 1) : v00;
+        const double v10 = two_y ? ortho_tap<DT>(img, at + pitch) : v00;
+        const double v11 = two_x && two_y ? ortho_tap<DT>(img, at + pitch + 1) : v00;
+        const double top = two_x ? v00 + fx * (v01 - v00) : v00;
+        const double bot = two_x ? v10 + fx * (v11 - v10) : v10;
+        val = two_y ? top + fy * (bot - top) : top;
+        return !(v00 == nd || v01 == nd || v10 == nd || v11 == nd);
+    }
+    // Catmull-Rom: rows y0 - 1 .. y0 + 2 (y0 alone with fy == 0), columns likewise
+    const double ly = two_y ? 1.0 : 0.0, hy = two_y ? 3.0 : 1.0, lx = two_x ? 1.0 : 0.0, hx = two_x ? 3.0 : 1.0;
+    if (!(y0 >= ly && x0 >= lx && y0 <= (double)rows - hy && x0 <= (double)cols - hx)) return false;
+    const long at = (long)(int)y0 * pitch + (int)x0;
+    const double wx[4] = {((-0.5 * fx + 1.0) * fx - 0.5) * fx, (1.5 * fx - 2.5) * fx * fx + 1.0, ((-1.5 * fx + 2.0) * fx + 0.5) * fx,
+                          (0.5 * fx - 0.5) * fx * fx};
+    const double wy[4] = {((-0.5 * fy + 1.0) * fy - 0.5) * fy, (1.5 * fy - 2.5) * fy * fy + 1.0, ((-1.5 * fy + 2.0) * fy + 0.5) * fy,
+                          (0.5 * fy - 0.5) * fy * fy};
+    bool ok = true;
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!two_y && j != 1) continue;
+        const long rb = at + (long)(j - 1) * pitch;
+        double rs;
+        if (two_x) {
+            const double v0 = ortho_tap<DT>(img, rb - 1), v1 = ortho_tap<DT>(img, rb), v2 = ortho_tap<DT>(img, rb + 1),
+                         v3 = ortho_tap<DT>(img, rb + 2);
+            ok = ok && !(v0 == nd || v1 == nd || v2 == nd || v3 == nd);
+            rs = wx[0] * v0 + wx[1] * v1 + wx[2] * v2 + wx[3] * v3;
+        } else {
+            rs = ortho_tap<DT>(img, rb);
+            ok = ok && !(rs == nd);
+        }
+        sum = two_y ? sum + wy[j] * rs : rs;
+    }
+    val = sum;
+    return ok;
+}
+
+template <int RS>
+__global__ __launch_bounds__(256) void ortho_rpc_kernel(const float* __restrict__ dsm, int rows, int cols, double gx0, double dx,
+                                                        double gy0, double dy, int crs, double lon0_deg, double false_northing,
+                                                        double dsm_nodata, double height_offset,
+                                                        const rd_ortho_view* __restrict__ views, int n_views, float fill,
+                                                        float* __restrict__ out, uint8_t* __restrict__ valid,
+                                                        double* __restrict__ coords, int tiles_x) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int tyi = blockIdx.x / tiles_x, txi = blockIdx.x - tyi * tiles_x;
+    const long c = (long)txi * ORTHO_TW + (w % ORTHO_WX) * ORTHO_FW + lane % ORTHO_FW;
+    const long r = (long)tyi * ORTHO_TH + (w / ORTHO_WX) * ORTHO_FH + lane / ORTHO_FW;
+    if (r >= rows || c >= cols) return;
+    const long plane = (long)rows * cols, i = r * cols + c;
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    const double z = (double)ld_nt1(dsm + i);
+    const bool zok = !(isnan(z) || z == dsm_nodata);
+    double lon = gx0 + ((double)c + 0.5) * dx, lat = gy0 + ((double)r + 0.5) * dy;
+    if (crs == RD_ORTHO_UTM) ortho_utm_inverse(lon, lat, lon0_deg, false_northing, lon, lat);
+    const double h = z + height_offset;
+    for (int v = 0; v < n_views; ++v) {                                         // n_views is an argument: the same for every thread
+        const rd_ortho_view& V = views[v];
+        const double P = (lat - V.lat_off) / V.lat_scale, L = (lon - V.lon_off) / V.lon_scale, H = (h - V.height_off) / V.height_scale;
+        const double LL = L * L, PP = P * P, HH = H * H;
+        const double m[20] = {1.0, L, P, H, L * P, L * H, P * H, LL, PP, HH, P * L * H, LL * L, L * PP, L * HH, LL * P, PP * P,
+                              P * HH, LL * H, PP * H, HH * H};
+        const double line = ortho_poly(V.line_num, m) / ortho_poly(V.line_den, m) * V.line_scale + V.line_off;
+        const double samp = ortho_poly(V.samp_num, m) / ortho_poly(V.samp_den, m) * V.samp_scale + V.samp_off;
+        const double yi = line - V.line0, xi = samp - V.samp0;
+        const void* img = V.image;
+        const long pitch = V.pitch;
+        const int ir = V.rows, ic = V.cols, dt = V.dtype;
+        const double nd = V.image_nodata;
+        bool ok = zok && img && ir >= 1 && ic >= 1;
+        double val = 0.0;
+        if (ok) {
+            if (dt == RD_ORTHO_U8) ok = ortho_resample<RS, RD_ORTHO_U8>(img, pitch, ir, ic, nd, yi, xi, val);
+            else if (dt == RD_ORTHO_U16) ok = ortho_resample<RS, RD_ORTHO_U16>(img, pitch, ir, ic, nd, yi, xi, val);
+            else if (dt == RD_ORTHO_F32) ok = ortho_resample<RS, RD_ORTHO_F32>(img, pitch, ir, ic, nd, yi, xi, val);
+            else ok = false;
+        }
+        const long o = (long)v * plane + i;
+        st_nt1(out + o, ok ? (float)val : fill);
+        if (valid) st_nt_u8(valid + o, ok ? 1 : 0);
+        if (coords) {
+            st_nt_f64(coords + 2 * o, zok ? yi : nanv);
+            st_nt_f64(coords + 2 * o + 1, zok ? xi : nanv);
+        }
+    }
+}
+
+}  // namespace rd
+
+extern "C" {
+
+int rd_ortho_rpc(const float* dsm, int rows, int cols, double x0, double dx, double y0, double dy, int crs, double lon0_deg,
+                 double false_northing, double dsm_nodata, double height_offset, const rd_ortho_view* views, int n_views,
+                 int resampling, float fill, float* out, uint8_t* valid, double* coords, rd_stream_t s_) {
+    constexpr double LARGEST = 1.7976931348623157e308;
+    RD_REQUIRE(dsm && views && out, "rd_ortho_rpc: null pointer (dsm, views or out)");
+    RD_REQUIRE(rows >= 1 && cols >= 1, "rd_ortho_rpc: bad shape (rows=%d cols=%d)", rows, cols);
+    RD_REQUIRE((long)rows * cols < (1l << 31), "rd_ortho_rpc: %d x %d pixels, fewer than 2^31 are taken", rows, cols);
+    RD_REQUIRE(n_views >= 1 && n_views <= RD_ORTHO_MAX_VIEWS, "rd_ortho_rpc: n_views %d outside 1..%d", n_views, RD_ORTHO_MAX_VIEWS);
+    RD_REQUIRE(dx != 0.0 && fabs(dx) <= LARGEST && dy != 0.0 && fabs(dy) <= LARGEST,
+               "rd_ortho_rpc: pixel size (%g, %g) must be non-zero and finite", dx, dy);
+    RD_REQUIRE(crs == RD_ORTHO_GEOGRAPHIC || crs == RD_ORTHO_UTM, "rd_ortho_rpc: unknown crs %d", crs);
+    RD_REQUIRE(resampling == RD_ORTHO_NEAREST || resampling == RD_ORTHO_BILINEAR || resampling == RD_ORTHO_BICUBIC,
+               "rd_ortho_rpc: unknown resampling %d", resampling);
+    RD_REQUIRE(fabs(lon0_deg) <= LARGEST && fabs(height_offset) <= LARGEST,
+               "rd_ortho_rpc: lon0_deg %g and height_offset %g must be finite", lon0_deg, height_offset);
+    hipStream_t s = (hipStream_t)s_;
+    const long tiles_x = ((long)cols + ORTHO_TW - 1) / ORTHO_TW, tiles_y = ((long)rows + ORTHO_TH - 1) / ORTHO_TH;
+    const double n = (double)rows * cols;
+    // the model of the header's cost: ~250 fp64 operations for the ground point, ~130 per view; the DSM once, out (+ valid, coords)
+    ProfScope ps(s, "ortho_rpc", n * (250.0 + 130.0 * n_views), n * (4.0 + n_views * (4.0 + (valid ? 1.0 : 0.0) + (coords ? 16.0 : 0.0))));
+    const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);                 // at most rows * cols < 2^31 tiles
+    if (resampling == RD_ORTHO_NEAREST)
+        RD_LAUNCH(ortho_rpc_kernel<RD_ORTHO_NEAREST>, grid, block, 0, s, dsm, rows, cols, x0, dx, y0, dy, crs, lon0_deg,
+                  false_northing, dsm_nodata, height_offset, views, n_views, fill, out, valid, coords, (int)tiles_x);
+    else if (resampling == RD_ORTHO_BILINEAR)
+        RD_LAUNCH(ortho_rpc_kernel<RD_ORTHO_BILINEAR>, grid, block, 0, s, dsm, rows, cols, x0, dx, y0, dy, crs, lon0_deg,
+                  false_northing, dsm_nodata, height_offset, views, n_views, fill, out, valid, coords, (int)tiles_x);
+    else
+        RD_LAUNCH(ortho_rpc_kernel<RD_ORTHO_BICUBIC>, grid, block, 0, s, dsm, rows, cols, x0, dx, y0, dy, crs, lon0_deg,
+                  false_northing, dsm_nodata, height_offset, views, n_views, fill, out, valid, coords, (int)tiles_x);
+    RD_LAUNCH_CHECK("ortho_rpc");
     return RD_OK;
 }
 
